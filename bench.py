@@ -20,8 +20,12 @@ Launch:  python bench.py --gpus N --steps K --warmup W
    SURVEY 8e) -> weak scaling, value = total tokens/s of all replicas.
    --parallelism tp: Megatron TP over RCCL (strong scaling), for reference.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), extended with
-"roofline" (dominant kernel, live HIP-event timing) and "cpu_baseline".
+A plain run sets up, warms up, times K steps and prints ONE JSON line on rank 0
+(metric, value, unit, ms_per_step, the step's HBM fraction); --dump-outputs DIR
+also writes what the last timed step computed.  --full runs every other section
+afterwards and extends the line: "roofline" (dominant kernel, live HIP-event
+timing), "value_ops_path", "prefill_kernels", "prefill_e2e", "cpu_baseline",
+"legs" (FP8, ragged, TP shards) and, for N > 1, "tp_section".
 """
 import argparse
 import json
@@ -47,6 +51,16 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--warmup", type=int, default=8)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other section: the per-kernel roofline, the op-by-op path, the "
+                         "prefill kernels and end-to-end prefill, the CPU baselines, the extra legs (FP8, ragged, TP shards) and, "
+                         "for N > 1, the tensor-parallel section.  Off by default: a plain run sets up, warms up, times --steps "
+                         "steps and prints the line.  The --no-* switches below trim a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step handed its caller as DIR/<name>.npy (float32): "
+                         "the sampled tokens, the final hidden states, the advanced positions / sequence lengths and the K / V "
+                         "rows the step wrote into every layer's cache.  Same arguments, same inputs: two builds compare "
+                         "output for output")
     ap.add_argument("--sim-tp", type=int, default=0,
                     help="one-GPU shard bench: time ONE rank of a TP group of this size (real per-GPU shard shapes, every "
                          "all-reduce replaced by a launch that holds the stream for --sim-ar-us); configs[3]: --model "
@@ -89,7 +103,7 @@ def parse_args():
                     help="ragged context lengths randint(1, ctx) (seed 0; SURVEY 8d, the reference's "
                          "tests/benchmarks/kernels/paged_attention.py) instead of one length for every sequence")
     ap.add_argument("--no-extra-legs", action="store_true",
-                    help="skip the extra legs of the default run (FP8 configs, ragged batch, TP shards: each a child "
+                    help="skip the extra legs of a --full run of the default workload (FP8 configs, ragged batch, TP shards: each a child "
                          "process of this script, summarised under `legs` in the line)")
     ap.add_argument("--no-tp-section", action="store_true",
                     help="N > 1, replicas: skip the tensor-parallel section (TP = N timing, overlap A/B, all-reduce latencies)")
@@ -128,6 +142,16 @@ def build(args, device):
     mem0 = torch.cuda.memory_allocated(device)
     model = M.LlamaForCausalLM(cfg, qc, dtype, args.kv_cache_dtype)
     model.init_synthetic(device, seed=0)
+    # Random nibbles against random zero points give every group of a column a common offset: o_proj / down_proj put out
+    # rms ~4 000 where a trained layer puts out ~1, the f16 residual stream grows by ~6 500 a layer and passes 65 504 at layer 10
+    # -- half of the batch was NaN from there on, from the first step.  1/16 on the group scales of the two projections that
+    # write into the stream keeps every layer finite; the norms hand each layer the same input as before, the kernels,
+    # shapes and bytes of the step are untouched.  (Dense models only: a sparse MLP's step time follows its routing, which
+    # follows the values -- the Mixtral leg keeps the weights it has been timed on.)
+    for layer in ([] if cfg.num_local_experts else model.layers):
+        for lin in (getattr(layer, "o_proj", None), getattr(layer, "down_proj", None)):
+            if getattr(lin, "scales", None) is not None:
+                lin.scales.data.mul_(1.0 / 16)
     if os.environ.get("APHRO_NO_FUSED_ROPE"):
         for layer in model.layers:
             layer.fuse_rope_attention = False
@@ -180,6 +204,10 @@ class DecodeLoop:
                                        device=device)
         self.next_ids = torch.zeros_like(self.input_ids)
         self.sampling = args.sampling
+        # --dump-outputs: keep the step's final hidden states (under graph replay: the capture's output buffer, rewritten by
+        # every replay); otherwise the step holds nothing back, as before
+        self.keep_hidden = bool(getattr(args, "dump_outputs", None))
+        self.hidden = None
         if self.sampling == "random":
             self.temperature = torch.full((args.batch, ), 0.8, device=device)
             self.top_k = torch.full((args.batch, ), 50, dtype=torch.int32, device=device)
@@ -189,6 +217,8 @@ class DecodeLoop:
     def step(self):
         m = self.meta
         hidden = self.model(self.input_ids, self.positions, self.kv_caches, m)
+        if self.keep_hidden:
+            self.hidden = hidden
         if self.sampling == "random":
             from aphrodite_engine_amd import _custom_ops as ops_
             logits = self.model.compute_logits(hidden)
@@ -207,6 +237,32 @@ class DecodeLoop:
         ops.advance_step_flashattn(self.input_ids.shape[0], self.input_ids.shape[0], self.block_size,
                                    self.input_ids, self.next_ids, self.positions, m.seq_lens_tensor,
                                    m.slot_mapping, m.block_tables)
+
+
+def dump_outputs(out_dir, loop, kv_cache_dtype):
+    """--dump-outputs: what the last timed step handed its caller, one float32 ``<name>.npy`` each (a few MB in all):
+    next_token_ids [bs] (also the next step's input ids), hidden_states [bs, hidden] (the model's output before the LM
+    head), positions / seq_lens [bs] as advanced for the next step, and k_last / v_last [layers, bs, kv_heads * head_dim]:
+    the rows the step wrote into every layer's paged cache (FP8 caches decoded to their values).  Called straight after
+    the timed region, before any other section runs a step."""
+    import numpy as np
+    from aphrodite_engine_amd.attention.paged_attn import PagedAttention
+    torch.cuda.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+    m, bs, l0 = loop.meta, loop.input_ids.shape[0], loop.model.layers[0]
+    pos = loop.positions - 1            # advance_step has moved on: the last step's token sits one position back
+    blk = m.block_tables[torch.arange(bs, device=pos.device), pos // loop.block_size].long()
+    off = pos % loop.block_size
+    f8 = {"fp8": torch.float8_e4m3fn, "fp8_e5m2": torch.float8_e5m2}.get(kv_cache_dtype)
+    k_last, v_last = [], []
+    for cache in loop.kv_caches:
+        kc, vc = PagedAttention.split_kv_cache(cache if f8 is None else cache.view(f8), l0.num_kv_heads, l0.head_dim)
+        k_last.append(kc[blk, :, :, off].float().reshape(bs, -1))      # [bs, heads, D / x, x] -> [bs, heads * D]
+        v_last.append(vc[blk, :, :, off].float().reshape(bs, -1))
+    arrays = {"next_token_ids": loop.next_ids, "hidden_states": loop.hidden, "positions": loop.positions,
+              "seq_lens": m.seq_lens_tensor, "k_last": torch.stack(k_last), "v_last": torch.stack(v_last)}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 def gemm_bytes(lin, M_rows):
@@ -1035,7 +1091,7 @@ def main_dry_cpu(args):
                 "unit": "tokens/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
                 "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "dry run", "data": "none",
                 "config": {"workload": "DRY RUN on CPU (control flow only)", "INVALID": "dry run"}, "process_group": pg}
-    if world > 1 and not args.no_tp_section:
+    if args.full and world > 1 and not args.no_tp_section:
         tp = run_tp_children(sys.argv[1:], world, rank)
         if rank == 0:
             line["tp_section"] = tp
@@ -1097,7 +1153,10 @@ def main():
 
     model, cfg, dtype = build(args, device)
     ops_path = world == 1 and not args.no_ops_path and args.model == "llama3-8b" and args.sim_tp <= 1
+    # (room for the op-by-op leg's steps whether or not --full runs it: the block tables and the capture-time maximum
+    #  length of the timed step do not depend on --full)
     total = (args.warmup + args.steps + 4) * (2 if ops_path else 1)
+    ops_path = ops_path and args.full
     loop = DecodeLoop(model, cfg, dtype, args, device, total)
 
     with torch.no_grad():
@@ -1125,11 +1184,13 @@ def main():
         elapsed = timed_region(run, args.steps, world, torch.cuda.synchronize, max_dev)
         if ca is not None:
             ca.check()      # a timed-out barrier would have produced garbage: fail loudly
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, loop, args.kv_cache_dtype)
         ctx_end = int(loop.meta.seq_lens_tensor[0].item())
         ctx_mean_end = float(loop.meta.seq_lens_tensor.float().mean().item())
         ctx_mean_start = loop.ctx_sum0 / args.batch
         active_frac = 1.0
-        if cfg.num_local_experts:
+        if cfg.num_local_experts and args.full:
             # experts the decode step really routes to (one more eager step with the routing recorded)
             for layer in model.layers:
                 layer.experts.record_routing = True
@@ -1140,14 +1201,14 @@ def main():
             for layer in model.layers:
                 layer.experts.record_routing = False
         ar_info = None
-        if tp > 1:
+        if tp > 1 and args.full:
             if overlap is not None:
                 D.enable_all_reduce_overlap(device, enabled=False)     # measure the bare collective
             try:
                 ar_info = all_reduce_section(args, model, device, ca)
             except Exception as e:
                 ar_info = {"error": repr(e)[:200]}
-        roof = roofline_section(model, loop, args) if rank == 0 else None
+        roof = roofline_section(model, loop, args) if rank == 0 and args.full else None
         # (the per-kernel section above runs on the allocations the timed step ran on; the op-by-op leg below releases and
         #  rebuilds every decode layout, which moves them -- round 6, profiles/r6_one_copy.txt)
         # ---- the same workload on the OP-BY-OP path: what a reference LlamaDecoderLayer (modeling/models/llama.py:234,
@@ -1203,6 +1264,8 @@ def main():
         tp_eff = max(tp, args.sim_tp, 1)
         kv_bytes = args.batch * ctx_mid * 2 * max(1, cfg.num_key_value_heads // tp_eff) * cfg.head_dim * esz * cfg.num_hidden_layers
         step_bytes = w_bytes + lm_head + kv_bytes
+    roofline = roofline_all = None
+    if rank == 0 and roof is not None:      # --full: the per-kernel section ran
         # dominant kernel = the kernel TEMPLATE with the largest total time per step: several
         # projections may run one template (qkv / o / down on wna16_gemm_kernel); its roofline point is their summed
         # algorithmic bytes over their summed launch time, per launch the average.
@@ -1254,6 +1317,17 @@ def main():
                                         "command on the round's last tree; NOT measured in this process)"}
         except Exception:
             traced = None
+        roofline = {"bound": "hbm", "kernel": dom_name, "members": dom["members"], "achieved": achieved, "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                    "bytes_per_launch": dom["bytes"] / n_members, "avg_launch_us": dom["seconds"] / n_members * 1e6,
+                    "total_us_per_layer": dom["seconds"] * 1e6, "traced": traced,
+                    # the whole step against the same peak (the headline fraction; `frac` is the dominant kernel's)
+                    "step_frac": step_bytes / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS}
+        roofline_all = {k: {"GBps": v["bytes"] / v["seconds"] / 1e9, "frac": v["bytes"] / v["seconds"] / 1e9 / HBM_PEAK_GBS,
+                            "bytes": v["bytes"], "avg_us": v["seconds"] * 1e6,
+                            **({"active_experts": v["active_experts"]} if "active_experts" in v else {})}
+                        for k, v in roof.items()}
+    if rank == 0:
         line = {
             "metric": "output tokens/sec + HBM-roofline %, Llama-3-8B int4/fp8 @ 1/2/4/8 MI355X",
             "value": tokens / elapsed,
@@ -1290,17 +1364,11 @@ def main():
                          "weight_bytes_one_copy": w_bytes + lm_head + model.embed_tokens.numel() * 2,
                          "weight_bytes_resident": weight_bytes_resident, "achieved_GBps": step_bytes / (elapsed / args.steps) / 1e9,
                          "frac_of_peak": step_bytes / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS},
-            "roofline": {"bound": "hbm", "kernel": dom_name, "members": dom["members"], "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                         "bytes_per_launch": dom["bytes"] / n_members, "avg_launch_us": dom["seconds"] / n_members * 1e6,
-                         "total_us_per_layer": dom["seconds"] * 1e6, "traced": traced,
-                         # the whole step against the same peak (the headline fraction; `frac` is the dominant kernel's)
-                         "step_frac": step_bytes / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS},
-            "roofline_all": {k: {"GBps": v["bytes"] / v["seconds"] / 1e9, "frac": v["bytes"] / v["seconds"] / 1e9 / HBM_PEAK_GBS,
-                                 "bytes": v["bytes"], "avg_us": v["seconds"] * 1e6,
-                                 **({"active_experts": v["active_experts"]} if "active_experts" in v else {})}
-                             for k, v in roof.items()},
         }
+        if cfg.num_local_experts and not args.full:
+            del line["step_hbm"]        # its bytes need the routed-expert fraction: one more step with the routing recorded (--full)
+        if roofline is not None:
+            line["roofline"], line["roofline_all"] = roofline, roofline_all
         if elapsed_ops is not None:
             line["value_ops_path"] = args.batch * args.steps / elapsed_ops
             line["ops_path"] = {"ms_per_step": elapsed_ops / args.steps * 1e3,
@@ -1322,7 +1390,7 @@ def main():
                                       "GPU's own memory (no link time: a lower bound); tokens/s is what the TP group would deliver "
                                       "at that all-reduce latency; outputs are not meaningful (the sums are over copies of one partial)")
 
-    if world > 1 and tp == 1 and not args.no_tp_section and args.model == "llama3-8b":
+    if args.full and world > 1 and tp == 1 and not args.no_tp_section and args.model == "llama3-8b":
         # free the replica first; the sharded model runs in CHILD processes (run_tp_children): whatever happens there, the
         # replica numbers above are already measured and the line below is printed
         loop = model = None
@@ -1338,7 +1406,8 @@ def main():
             dist.barrier()
             dist.destroy_process_group()
         return
-    if world == 1 and not args.no_prefill_info and args.model == "llama3-8b":
+    one_gpu_sections = args.full and world == 1         # (a plain run goes straight to its line)
+    if one_gpu_sections and not args.no_prefill_info and args.model == "llama3-8b":
         try:
             del loop, model               # the decode state is no longer needed: give its memory back first
             torch.cuda.empty_cache()
@@ -1364,13 +1433,13 @@ def main():
                 line["prefill_e2e"] = prefill_e2e_section()
             except Exception as e:
                 line["prefill_e2e"] = {"error": repr(e)[:300]}
-    if world == 1 and not args.no_cpu_baseline and args.model == "llama3-8b":
+    if one_gpu_sections and not args.no_cpu_baseline and args.model == "llama3-8b":
         try:
             line["cpu_baseline"] = cpu_baseline(args, cfg)
         except Exception as e:  # never lose the GPU number to a CPU-side problem
             line["cpu_baseline"] = {"value": None, "unit": "tokens/s", "cores": os.cpu_count(),
                                     "kind": "port", "sample": f"failed: {e!r}"}
-    if world == 1 and default_workload(args) and not args.no_extra_legs and not os.environ.get("APHRO_BENCH_LEG"):
+    if one_gpu_sections and default_workload(args) and not args.no_extra_legs and not os.environ.get("APHRO_BENCH_LEG"):
         line["legs"] = extra_legs(args)
         # the FP8 half of the metric next to the int4 headline
         line["fp8"] = {k: line["legs"][k] for k in ("fp8_w8a8_fp8kv_ctx8192", "fp8_w8a8_ctx1024") if k in line["legs"]}
@@ -1381,13 +1450,13 @@ def main():
 
 
 def default_workload(args) -> bool:
-    """True for the driver's command (`bench.py --gpus 1 --steps K --warmup W`): the extra legs ride on that line only."""
+    """True for the driver's workload (`bench.py --gpus 1 --steps K --warmup W`): under --full the extra legs ride on that line only."""
     return (args.model == "llama3-8b" and args.quant == "gptq" and args.kv_cache_dtype == "auto" and args.batch == 32
             and args.ctx == 1024 and args.sim_tp <= 1 and not args.ragged and not args.layers and not args.no_graph
             and args.sampling == "greedy")
 
 
-# The legs of the default run: BASELINE.json configs[2] (FP8 weights + FP8 KV at 8192 tokens), the FP8 model at the
+# The legs of a --full run of the default workload: BASELINE.json configs[2] (FP8 weights + FP8 KV at 8192 tokens), the FP8 model at the
 # headline's context, a ragged batch of the headline workload, and ONE rank of configs[3] / configs[4] (real shard shapes,
 # all-reduces replaced by a stream-holding stub -- no multi-GPU box has been available to this project).  Each leg is this
 # script again in a child process (own HIP context, the parent's model already freed), timed exactly like the headline.
@@ -1407,7 +1476,7 @@ def extra_legs(args):
     budget_s = float(os.environ.get("APHRO_BENCH_LEG_TIMEOUT_S", "150"))
     for name, extra in LEGS.items():
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(args.steps), "--warmup", str(args.warmup),
-               "--no-cpu-baseline", "--no-prefill-info", "--no-ops-path", "--no-prefill-e2e"] + extra
+               "--full", "--no-cpu-baseline", "--no-prefill-info", "--no-ops-path", "--no-prefill-e2e"] + extra     # (its roofline)
         try:
             r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=budget_s)
             rec = None

@@ -617,7 +617,7 @@ def test_int4_expert_methods_refuse_group_sizes_the_grouped_kernel_does_not_serv
 
 
 # ---- bench.py --gpus 2: the driver's launch form, control flow only -----------------------------
-def _run_bench_dry(extra_env, timeout=180):
+def _run_bench_dry(extra_env, timeout=180, full=True):
     import json
     import os
     import socket
@@ -630,6 +630,7 @@ def _run_bench_dry(extra_env, timeout=180):
     env = dict(os.environ, APHRO_BENCH_DRY_CPU="1", **extra_env)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"]
+    cmd += ["--full"] if full else []          # the tensor-parallel section is one of --full's
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout, cwd=root)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0, r.stderr[-2000:]
@@ -638,13 +639,20 @@ def _run_bench_dry(extra_env, timeout=180):
 
 
 def test_bench_two_ranks_control_flow_over_gloo():
-    """`python -m torch.distributed.run --nproc-per-node 2 bench.py --gpus 2 ...` exactly as the driver launches it, with a stub
+    """`python -m torch.distributed.run --nproc-per-node 2 bench.py --gpus 2 ... --full`, the driver's launch form, with a stub
     in place of the model (APHRO_BENCH_DRY_CPU): process group, barrier + max-over-ranks timing, the tensor-parallel section in
     child processes on their own rendezvous, one line from rank 0 with whole-job throughput."""
     line = _run_bench_dry({})
     assert line["n_gpus"] == 2 and line["steps"] == 3 and line["warmup"] == 1 and line["value"] > 0
     assert line["process_group"]["backend"] == "gloo" and line["process_group"]["world"] == 2
     assert line["tp_section"] == {"tp": 2, "backend": "gloo", "ranks_seen_by_collective": 2, "dry_run": True}
+
+
+def test_bench_plain_run_times_its_steps_and_nothing_else():
+    """Without --full the same launch prints the replica line alone: no tensor-parallel children are started."""
+    line = _run_bench_dry({"APHRO_BENCH_DRY_TP_FAIL": "raise"}, full=False)       # (a child, if started, would fail loudly)
+    assert line["n_gpus"] == 2 and line["steps"] == 3 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert "tp_section" not in line
 
 
 @pytest.mark.parametrize("failure", ["crash", "raise", "hang"])

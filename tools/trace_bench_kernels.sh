@@ -2,7 +2,7 @@
 out=gpurun_out/$1; shift
 mkdir -p $out
 export TMPDIR=/tmp
-timeout 280 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o t -- python bench.py --gpus 1 --steps 20 --warmup 5 --no-prefill-info --no-ops-path --no-cpu-baseline "$@" > $out/line.json 2> $out/err.txt
+timeout 280 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o t -- python bench.py --gpus 1 --steps 20 --warmup 5 --full --no-prefill-info --no-ops-path --no-cpu-baseline "$@" > $out/line.json 2> $out/err.txt
 find $out/prof -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $out/kernel_stats.csv
 rm -rf $out/prof
 python - $out/kernel_stats.csv <<'P'
