@@ -688,6 +688,46 @@ GPTQ_DEQUANT_MIN_M = 256
 SCALED_MM_LIBRARY_MIN_M = 64   # above this the fp8 GEMM goes to hipBLASLt (torch._scaled_mm)
 
 
+# Rows up to which the checkpoint-order (g_idx) kernel serves gptq_gemm(use_exllama=False, bit=4), in 32-row passes; above
+# it the weight is reconstructed once + a library GEMM (the reference's own rule).  Measured: tools/gptq_gidx_bench.py,
+# profiles/gptq_gidx_gemm.txt (DESIGN.md "gptq_gidx_gemm").  csrc_torch/torch_bindings.cpp carries the same number.
+GPTQ_GIDX_MAX_M = 64
+
+
+def gptq_gidx_ok(m: int, n: int, k: int, groups: int, dtype: torch.dtype) -> bool:
+    return dtype in _DT and bool(_lib.lib().aphro_gptq_gemm_gidx_supported(min(m, 32), n, k, groups, _dt_of(dtype)))
+
+
+def gptq_gemm_gidx(a: torch.Tensor, qweight: torch.Tensor, qzeros: torch.Tensor, scales: torch.Tensor,
+                   g_idx: torch.Tensor, zero_offset: int = 1) -> torch.Tensor:
+    """a [M, K] x 4-bit GPTQ weights in CHECKPOINT order with the per-row group map g_idx [K] (act-order shards under
+    row-parallel TP; the reference's gemm_half_q_half_alt_4bit_kernel, q_gemm.cu:1184-1281): csrc/gptq_gidx_gemm.hip,
+    32 rows per launch.  scales / qzeros keep the groups of the unsharded matrix."""
+    _require_cuda(a, qweight, qzeros, scales, g_idx)
+    m, k = a.shape
+    n, groups = qweight.shape[1], scales.shape[0]
+    if a.dtype != scales.dtype:
+        raise RuntimeError("gptq_gemm_gidx: activations and scales must share a dtype")
+    if qweight.shape[0] * 8 != k or g_idx.numel() != k or tuple(qzeros.shape) != (groups, n // 8) or scales.shape[1] != n:
+        raise RuntimeError("gptq_gemm_gidx: shape mismatch")
+    out = torch.empty((m, n), dtype=a.dtype, device=a.device)
+    if m == 0:
+        return out
+    if not gptq_gidx_ok(m, n, k, groups, a.dtype):
+        raise RuntimeError(f"gptq_gemm_gidx: M={m} N={n} K={k} groups={groups} {a.dtype} is not served by the kernel")
+    if a.stride(1) != 1 or a.stride(0) % 8 != 0 or a.data_ptr() % 16 != 0:
+        a = a.contiguous()
+    g_idx = g_idx.to(torch.int32).contiguous()
+    qweight, qzeros, scales = qweight.contiguous(), qzeros.contiguous(), scales.contiguous()
+    lib = _lib.lib()
+    ws = _workspace(a.device, lib.aphro_gptq_gemm_gidx_workspace_bytes(min(m, 32), n, k))
+    for m0 in range(0, m, 32):
+        check(lib.aphro_gptq_gemm_gidx(a[m0:].data_ptr(), a.stride(0), qweight.data_ptr(), qzeros.data_ptr(),
+                                       scales.data_ptr(), g_idx.data_ptr(), out[m0:].data_ptr(), ws.data_ptr(), ws.numel(),
+                                       min(32, m - m0), n, k, groups, zero_offset, _dt(a), _stream()), "gptq_gemm_gidx")
+    return out
+
+
 def gptq_gemm(a: torch.Tensor, b_q_weight: torch.Tensor,
               b_gptq_qzeros: torch.Tensor, b_gptq_scales: torch.Tensor,
               b_g_idx: torch.Tensor, use_exllama: bool, bit: int) -> torch.Tensor:
@@ -699,6 +739,9 @@ def gptq_gemm(a: torch.Tensor, b_q_weight: torch.Tensor,
     if bit != 4:
         raise RuntimeError(f"gptq_gemm: weight width {bit} is not one of 2, 3, 4, 8")
     m = a.shape[0]
+    if not use_exllama and b_g_idx is not None and b_g_idx.numel() > 0 and 0 < m <= GPTQ_GIDX_MAX_M and \
+            gptq_gidx_ok(m, b_q_weight.shape[1], a.shape[1], b_gptq_scales.shape[0], a.dtype):
+        return gptq_gemm_gidx(a, b_q_weight, b_gptq_qzeros, b_gptq_scales, b_g_idx, 1)
     large = use_exllama and wna16_large_ok(m, b_q_weight.shape[1], a.shape[1], b_gptq_scales.shape[0]) \
         and wna16_prefers_large(m, b_q_weight.shape[1], a.shape[1]) and not switch("APHRO_WNA16_NO_LARGE")
     if not use_exllama or (m >= GPTQ_DEQUANT_MIN_M and not large):

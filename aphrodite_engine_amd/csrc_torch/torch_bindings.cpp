@@ -40,13 +40,44 @@ void ok(int rc, const char* op) { TORCH_CHECK(rc == APHRO_OK, op, ": ", aphro_la
 // gptq_gemm (q_gemm.cu:1824-1859): c [M, N] in a's dtype
 torch::Tensor gptq_gemm(torch::Tensor a, torch::Tensor b_q_weight, torch::Tensor b_gptq_qzeros, torch::Tensor b_gptq_scales,
                         torch::Tensor b_g_idx, bool use_exllama, int64_t bit) {
-  TORCH_CHECK(use_exllama && (bit == 2 || bit == 3 || bit == 4 || bit == 8),
-              "gptq_gemm on MI355X: exllama-shuffled 2 / 3 / 4 / 8-bit weights (the non-exllama form is served by the Python op)");
+  TORCH_CHECK(bit == 2 || bit == 3 || bit == 4 || bit == 8, "gptq_gemm: weight width ", bit, " is not one of 2, 3, 4, 8");
+  TORCH_CHECK(use_exllama || bit == 4,
+              "gptq_gemm on MI355X: the non-exllama form is served at 4 bits (2 / 3 / 8-bit checkpoint-order weights go through the Python op)");
   TORCH_CHECK(a.is_cuda() && a.dim() == 2 && a.stride(1) == 1, "gptq_gemm: a must be a row-major device matrix");
   const int64_t m = a.size(0), k = a.size(1), n = b_q_weight.size(1);
   auto out = torch::empty({m, n}, a.options());
   const bool act_order = b_g_idx.numel() > 0 && b_g_idx.device().is_cuda();
   const int64_t groups = b_gptq_scales.size(0);
+  if (!use_exllama) {
+    // checkpoint order, groups through g_idx (act-order shards under row-parallel TP: `groups` is that of the unsharded
+    // matrix, no relation to K): csrc/gptq_gidx_gemm.hip up to GIDX_MAX_M rows (the Python op's GPTQ_GIDX_MAX_M), else the
+    // weight reconstructed once + a library GEMM (q_gemm.cu:1529-1544)
+    constexpr int64_t GIDX_MAX_M = 64;
+    TORCH_CHECK(groups > 0 && b_q_weight.size(0) * 8 == k, "gptq_gemm: q_weight [K/8, N] and scales [groups, N] expected");
+    const int dt = act_dtype(a);
+    torch::Tensor gi = act_order ? b_g_idx.to(torch::kInt).contiguous() : torch::Tensor();
+    if (act_order && m >= 1 && m <= GIDX_MAX_M && aphro_gptq_gemm_gidx_supported(m < 32 ? m : 32, n, k, groups, dt)) {
+      TORCH_CHECK(gi.numel() == k, "gptq_gemm: g_idx must have K entries");
+      torch::Tensor x = (a.stride(0) % 8 != 0 || ((uintptr_t)a.data_ptr() % 16) != 0) ? a.contiguous() : a;
+      auto ws = torch::empty({(int64_t)aphro_gptq_gemm_gidx_workspace_bytes(m < 32 ? m : 32, n, k)}, a.options().dtype(torch::kUInt8));
+      for (int64_t m0 = 0; m0 < m; m0 += 32) {
+        const int64_t rows = m - m0 < 32 ? m - m0 : 32;
+        ok(aphro_gptq_gemm_gidx((const char*)x.data_ptr() + m0 * x.stride(0) * x.element_size(), x.stride(0),
+                                (const uint32_t*)b_q_weight.data_ptr(), (const uint32_t*)b_gptq_qzeros.data_ptr(),
+                                b_gptq_scales.data_ptr(), (const int32_t*)gi.data_ptr(),
+                                (char*)out.data_ptr() + m0 * n * out.element_size(), ws.data_ptr(), (size_t)ws.numel(), rows, n, k,
+                                groups, 1, dt, cur_stream()),
+           "gptq_gemm");
+      }
+      return out;
+    }
+    TORCH_CHECK(act_order || k % groups == 0, "gptq_gemm: without g_idx the groups must divide K (groups=", groups, ", K=", k, ")");
+    auto w = torch::empty({k, n}, a.options());
+    ok(aphro_gptq_dequant((const uint32_t*)b_q_weight.data_ptr(), (const uint32_t*)b_gptq_qzeros.data_ptr(), b_gptq_scales.data_ptr(),
+                          act_order ? (const int32_t*)gi.data_ptr() : nullptr, w.data_ptr(), k, n, groups, 0, 1, dt, cur_stream()),
+       "gptq_gemm");
+    return torch::matmul(a, w);
+  }
   TORCH_CHECK(groups > 0 && k % groups == 0, "gptq_gemm: scales [groups, N] with groups dividing K (groups=", groups, ", K=", k, ")");
   if (bit != 4) {   // csrc/wnx_gemm.hip: MFMA small-M kernel on the sequential layout, else reconstruct + library GEMM
     torch::Tensor ag = act_order ? a.index_select(1, b_g_idx.to(torch::kLong)) : a;

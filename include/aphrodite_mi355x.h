@@ -868,6 +868,31 @@ int aphro_gptq_gemm_bits(const void* a, int64_t lda, const uint32_t* q_weight, c
 int aphro_gptq_make_sequential_bits(const uint32_t* q_weight, uint32_t* out, const int32_t* perm, int64_t K, int64_t N,
                                     int bits, void* stream);
 
+/* `_C::gptq_gemm` with use_exllama = false, bit = 4 at decode sizes: the role of gemm_half_q_half_alt_4bit_kernel
+ * (q_gemm.cu:1184-1281, launched by gemm_half_q_half_alt :1283-1310 for up to 8 rows), the kernel of act-order checkpoints
+ * under row-parallel TP (gptq.py:137-139 keeps those layers in checkpoint order).  csrc/gptq_gidx_gemm.hip.
+ *   c[M, N] = a[M, K] . W,  W[k][n] = (q[k][n] - (qzero[g_idx[k]][n] + zero_offset)) * scale[g_idx[k]][n]
+ * a: [M, lda] f16 | bf16 (lda in elements, lda % 8 == 0, 16-byte aligned); q_weight: int32 [K/8, N] in CHECKPOINT order
+ * (nibble i of word w = row 8w + i, not through gptq_shuffle); qzeros int32 [groups, N/8]; scales [groups, N] in a's
+ * dtype; g_idx int32 [K], row -> group.  `groups` is the group count of the UNSHARDED matrix: no relation to K is assumed.
+ * A g_idx entry outside [0, groups) is clamped (wrong numbers, no out-of-range read).  f16: every weight has the bits of
+ * aphro_gptq_dequant's; fp32 accumulation; bf16: activations and scales are converted to f16 (saturating), fp32
+ * accumulation, one rounding to bf16.  1 <= M <= 32 rows per call.  One launch: K slices are reduced inside the kernel in
+ * slice order (self-resetting tickets: safe under HIP-graph replay), no atomics on c, no host synchronisation, nothing
+ * allocated.  workspace: fp32 partials of the K slices, aphro_gptq_gemm_gidx_workspace_bytes(M, N, K) bytes, 16-byte
+ * aligned (APHRO_ERR_WORKSPACE without a launch when it is too small).
+ * aphro_gptq_gemm_gidx_supported: 1 exactly when the kernel takes the shape -- f16 | bf16, 1 <= M <= 32, N % 64 == 0
+ * (the column tile), K % 32 == 0 (the k-step), and the tile's scale / zero table of all groups fitting LDS beside the
+ * staged activations (groups <= 499). */
+int aphro_gptq_gemm_gidx_supported(int64_t M, int64_t N, int64_t K, int64_t groups, int dtype);
+/* Upper bound of the fp32 partial slabs of aphro_gptq_gemm_gidx (8 K slices x min(M, 32) x N floats; the alt kernel of
+ * the reference, q_gemm.cu:1283-1310, accumulates with atomics on c instead). */
+size_t aphro_gptq_gemm_gidx_workspace_bytes(int64_t M, int64_t N, int64_t K);
+/* The GEMM itself (q_gemm.cu:1184-1281); arguments above. */
+int aphro_gptq_gemm_gidx(const void* a, int64_t lda, const uint32_t* q_weight, const uint32_t* qzeros, const void* scales,
+                         const int32_t* g_idx, void* c, void* workspace, size_t workspace_bytes, int64_t M, int64_t N,
+                         int64_t K, int64_t groups, int zero_offset, int dtype, void* stream);
+
 /* FP8 W8A8 decode GEMM for M <= 32, one workgroup per CU on a strip-major copy of the weight (round 4,
  * csrc/fp8_gemm_resident.hip): same role and arithmetic as aphro_scaled_mm_fp8 / aphro_scaled_mm_fp8_slabs
  * (cutlass_scaled_mm, kernels/quantization/cutlass_w8a8/scaled_mm_entry.cu:92-137; torch._scaled_mm on ROCm,
