@@ -760,14 +760,57 @@ def gptq_gemm(a: torch.Tensor, b_q_weight: torch.Tensor,
     return _wna16(a, b_q_weight, b_gptq_qzeros, b_gptq_scales, perm, 1)
 
 
+# Rows at which 8-bit exllama-form weights go to the prompt-sized kernel (csrc/gptq8_gemm_large.hip) instead of gptq_dequant +
+# a library GEMM.  Measured on the Llama-3-8B projections (tools/gptq8_large_bench.py, profiles/gptq8_gemm_large.txt, DESIGN.md
+# "gptq8_gemm_large"): 1.2x .. 4.8x faster on every projection from 65 to 1024 rows; at 2048 rows qkv loses (0.82x), at 8192
+# every projection does (0.89x .. 0.95x: the library GEMM amortises the reconstruction), so above MAX_M the old path stays.
+# csrc_torch/torch_bindings.cpp carries the same numbers.
+GPTQ8_LARGE_MIN_M = 65
+GPTQ8_LARGE_MAX_M = 1024
+
+
+def gptq8_large_ok(m: int, n: int, k: int, groups: int, dtype: torch.dtype) -> bool:
+    return dtype in _DT and bool(_lib.lib().aphro_gptq8_gemm_large_supported(m, n, k, groups, _dt_of(dtype)))
+
+
+def gptq8_gemm_large(a: torch.Tensor, qweight: torch.Tensor, qzeros: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """a [M, K] x 8-bit GPTQ / uint8b128 weights in the sequential layout (qweight int32 [K/4, N] after gptq_shuffle(bit=8),
+    qzeros int32 [G, N/4] stored as zero - 1, scales [G, N]) for prompt-sized M: csrc/gptq8_gemm_large.hip.  Act-order: pass
+    a[:, perm]."""
+    _require_cuda(a, qweight, qzeros, scales)
+    m, k = a.shape
+    n, groups = qweight.shape[1], scales.shape[0]
+    if a.dtype != scales.dtype:
+        raise RuntimeError("gptq8_gemm_large: activations and scales must share a dtype")
+    if qweight.shape[0] * 4 != k or tuple(qzeros.shape) != (groups, n // 4) or scales.shape[1] != n:
+        raise RuntimeError("gptq8_gemm_large: shape mismatch")
+    out = torch.empty((m, n), dtype=a.dtype, device=a.device)
+    if m == 0:
+        return out
+    if not gptq8_large_ok(m, n, k, groups, a.dtype):
+        raise RuntimeError(f"gptq8_gemm_large: M={m} N={n} K={k} groups={groups} {a.dtype} is not served by the kernel")
+    if a.stride(1) != 1 or a.stride(0) % 8 != 0 or a.data_ptr() % 16 != 0:
+        a = a.contiguous()
+    qweight, qzeros, scales = qweight.contiguous(), qzeros.contiguous(), scales.contiguous()
+    lib = _lib.lib()
+    nbytes = lib.aphro_gptq8_gemm_large_workspace_bytes(m, n, k, groups, _dt(a))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=a.device)        # (the caching allocator: capturable)
+    check(lib.aphro_gptq8_gemm_large(a.data_ptr(), a.stride(0), qweight.data_ptr(), qzeros.data_ptr(), scales.data_ptr(),
+                                     out.data_ptr(), ws.data_ptr(), nbytes, m, n, k, groups, _dt(a), _stream()),
+          "gptq8_gemm_large")
+    return out
+
+
 def _gptq_gemm_bits(a, qweight, qzeros, scales, g_idx, use_exllama: bool, bit: int) -> torch.Tensor:
     """2 / 3 / 8-bit GPTQ (q_gemm.cu:329-700, 1526-1560): the MFMA small-M kernel on the sequential layout at <= 32 rows
-    (64 in two passes), else the weight reconstructed once (bit for bit the reference's reconstruct kernels) + a library
-    GEMM -- the reference's own rule above 50 (8-bit: 24) rows."""
+    (64 in two passes); 8-bit at GPTQ8_LARGE_MIN_M .. GPTQ8_LARGE_MAX_M rows the prompt-sized kernel; else the weight reconstructed once (bit
+    for bit the reference's reconstruct kernels) + a library GEMM -- the reference's own rule above 50 (8-bit: 24) rows."""
     lib = _lib.lib()
     m, k = a.shape
     n, groups = qweight.shape[1], scales.shape[0]
     has_perm = g_idx is not None and g_idx.numel() > 0
+    if bit == 8 and use_exllama and GPTQ8_LARGE_MIN_M <= m <= GPTQ8_LARGE_MAX_M and gptq8_large_ok(m, n, k, groups, a.dtype):
+        return gptq8_gemm_large(a[:, g_idx.long()] if has_perm else a, qweight, qzeros, scales)
     if use_exllama and 0 < m <= 64 and lib.aphro_gptq_gemm_bits_supported(min(m, 32), n, k, groups, bit):
         x = a[:, g_idx.long()] if has_perm else a           # act-order: gather once (q_gemm.cu:219-226)
         if x.stride(1) != 1 or x.stride(0) % 8 != 0 or x.data_ptr() % 16 != 0:

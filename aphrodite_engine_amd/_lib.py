@@ -129,6 +129,9 @@ SIGNATURES = {
     "aphro_gptq_gemm_bits_supported": (I, [L, L, L, L, I]),
     "aphro_gptq_gemm_bits": (I, [P, L, P, P, P, P, L, L, L, L, I, I, P]),
     "aphro_gptq_make_sequential_bits": (I, [P, P, P, L, L, I, P]),
+    "aphro_gptq8_gemm_large_supported": (I, [L, L, L, L, I]),
+    "aphro_gptq8_gemm_large_workspace_bytes": (Z, [L, L, L, L, I]),
+    "aphro_gptq8_gemm_large": (I, [P, L, P, P, P, P, P, Z, L, L, L, L, I, P]),
     "aphro_gptq_gemm_gidx_supported": (I, [L, L, L, L, I]),
     "aphro_gptq_gemm_gidx_workspace_bytes": (Z, [L, L, L]),
     "aphro_gptq_gemm_gidx": (I, [P, L, P, P, P, P, P, P, Z, L, L, L, L, I, I, P]),

@@ -93,6 +93,19 @@ torch::Tensor gptq_gemm(torch::Tensor a, torch::Tensor b_q_weight, torch::Tensor
       }
       return out;
     }
+    // 8 bits at prompt sizes: csrc/gptq8_gemm_large.hip at GPTQ8_LARGE_MIN_M .. GPTQ8_LARGE_MAX_M rows (the Python op's constants
+    // of the same names: the two must agree; measured, profiles/gptq8_gemm_large.txt)
+    constexpr int64_t GPTQ8_LARGE_MIN_M = 65, GPTQ8_LARGE_MAX_M = 1024;
+    if (bit == 8 && m >= GPTQ8_LARGE_MIN_M && m <= GPTQ8_LARGE_MAX_M && aphro_gptq8_gemm_large_supported(m, n, k, groups, act_dtype(a))) {
+      if (((uintptr_t)ag.data_ptr() % 16) != 0) ag = ag.clone();
+      auto ws8 = torch::empty({(int64_t)aphro_gptq8_gemm_large_workspace_bytes(m, n, k, groups, act_dtype(a))},
+                              a.options().dtype(torch::kUInt8));
+      ok(aphro_gptq8_gemm_large(ag.data_ptr(), ag.stride(0), (const uint32_t*)b_q_weight.data_ptr(),
+                                (const uint32_t*)b_gptq_qzeros.data_ptr(), b_gptq_scales.data_ptr(), out.data_ptr(), ws8.data_ptr(),
+                                (size_t)ws8.numel(), m, n, k, groups, act_dtype(a), cur_stream()),
+         "gptq_gemm");
+      return out;
+    }
     auto w = torch::empty({k, n}, a.options());
     ok(aphro_gptq_dequant_bits((const uint32_t*)b_q_weight.data_ptr(), (const uint32_t*)b_gptq_qzeros.data_ptr(),
                                b_gptq_scales.data_ptr(), nullptr, w.data_ptr(), k, n, groups, (int)bit, act_dtype(a), cur_stream()),

@@ -868,6 +868,28 @@ int aphro_gptq_gemm_bits(const void* a, int64_t lda, const uint32_t* q_weight, c
 int aphro_gptq_make_sequential_bits(const uint32_t* q_weight, uint32_t* out, const int32_t* perm, int64_t K, int64_t N,
                                     int bits, void* stream);
 
+/* 8-bit GPTQ / compressed-tensors uint8b128 weights at PROMPT sizes (M > 64): the role of reconstruct + hipBLAS in
+ * `_C::gptq_gemm` (q_gemm.cu:1526-1560) and of `_C::gptq_marlin_gemm` with an 8-bit type.  csrc/gptq8_gemm_large.hip.
+ *   c[M, N] = a[M, K] . W,  W[k][n] = (q[k][n] - (qzero[k / gs][n] + 1)) * scale[k / gs][n],  gs = K / groups
+ * a: [M, lda] f16 | bf16 (lda in elements, lda % 8 == 0, lda >= K, 16-byte aligned); act-order: pass a[:, perm].
+ * q_weight: int32 [K/4, N] in the sequential layout (after gptq_shuffle(bit = 8): word r of column n = k 4r .. 4r+3,
+ * little-endian bytes); qzeros int32 [groups, N/4], one byte per column, stored as zero - 1 (stored 255 means 256);
+ * scales [groups, N] in a's dtype; c [M, N] in a's dtype, 16-byte aligned.
+ * f16: every weight entering the MFMA has the bits of aphro_gptq_dequant_bits(bits = 8); fp32 accumulation, one rounding
+ * of the sum.  bf16: activations widened to f16 with saturation (into the workspace), scales converted to f16, fp32
+ * accumulation, output rounded to bf16 (RNE).  Small grids cut K into slices whose fp32 slabs (workspace) are added in
+ * slice order by a second launch: deterministic, bit-equal run to run, no flags or atomics -- replays under a HIP graph.
+ * aphro_gptq8_gemm_large_supported: 1 exactly when the kernel takes the shape -- f16 | bf16, M >= 1, N % 128 == 0,
+ * K % 64 == 0, K % groups == 0, group size a multiple of 64 (groups == 1, channel-wise, included), and a, q_weight, c
+ * and scales each below 4 GiB.
+ * aphro_gptq8_gemm_large_workspace_bytes: the f16 copy of bf16 activations + the fp32 slabs of the plan for the shape (0
+ * for an unsupported shape); workspace 16-byte aligned, APHRO_ERR_WORKSPACE without a launch when it is too small. */
+int aphro_gptq8_gemm_large_supported(int64_t M, int64_t N, int64_t K, int64_t groups, int dtype);
+size_t aphro_gptq8_gemm_large_workspace_bytes(int64_t M, int64_t N, int64_t K, int64_t groups, int dtype);
+int aphro_gptq8_gemm_large(const void* a, int64_t lda, const uint32_t* q_weight, const uint32_t* qzeros, const void* scales,
+                           void* c, void* workspace, size_t workspace_bytes, int64_t M, int64_t N, int64_t K,
+                           int64_t groups, int dtype, void* stream);
+
 /* `_C::gptq_gemm` with use_exllama = false, bit = 4 at decode sizes: the role of gemm_half_q_half_alt_4bit_kernel
  * (q_gemm.cu:1184-1281, launched by gemm_half_q_half_alt :1283-1310 for up to 8 rows), the kernel of act-order checkpoints
  * under row-parallel TP (gptq.py:137-139 keeps those layers in checkpoint order).  csrc/gptq_gidx_gemm.hip.
