@@ -728,6 +728,51 @@ def gptq_gemm_gidx(a: torch.Tensor, qweight: torch.Tensor, qzeros: torch.Tensor,
     return out
 
 
+# Rows at which the checkpoint-order (g_idx) form goes to the prompt-sized kernel (csrc/gptq_gidx_gemm_large.hip) instead of
+# gptq_dequant + a library GEMM.  Measured on the row-parallel projections of Llama-3-8B (TP 2) and a 70B (TP 8), act-order,
+# group 128 (tools/gptq_gidx_large_bench.py, profiles/gptq_gidx_gemm_large.txt, DESIGN.md "gptq_gidx_gemm_large"): 1.03x .. 1.75x
+# faster on all four shapes at 65, 96, 128, 129 and 136 rows in both runs (runs agree within 0.5 %).  At 144 rows the 8B o_proj
+# ties (0.996x in both runs), at 152 and 160 it wins again (1.01x, 1.18x: the library GEMM's time is not monotone in M), from
+# 176 rows it loses (0.90x .. 0.92x) while the other three win up to 256; from 512 rows every shape loses (0.72x .. 0.98x: the
+# kernel is VALU-bound at 0.2 of the MFMA peak).  MAX_M is the last measured row count below the first one that does not win;
+# above it the old path and its log line stay.  csrc_torch/torch_bindings.cpp carries the same numbers.
+GPTQ_GIDX_LARGE_MIN_M = 65
+GPTQ_GIDX_LARGE_MAX_M = 136
+
+
+def gptq_gidx_large_ok(m: int, n: int, k: int, groups: int, dtype: torch.dtype) -> bool:
+    return dtype in _DT and bool(_lib.lib().aphro_gptq_gemm_gidx_large_supported(m, n, k, groups, _dt_of(dtype)))
+
+
+def gptq_gemm_gidx_large(a: torch.Tensor, qweight: torch.Tensor, qzeros: torch.Tensor, scales: torch.Tensor,
+                         g_idx: torch.Tensor, zero_offset: int = 1) -> torch.Tensor:
+    """gptq_gemm_gidx's form (4-bit GPTQ weights in CHECKPOINT order, per-row group map g_idx [K], scales / qzeros of the
+    unsharded matrix) for prompt-sized M in one call: csrc/gptq_gidx_gemm_large.hip."""
+    _require_cuda(a, qweight, qzeros, scales, g_idx)
+    m, k = a.shape
+    n, groups = qweight.shape[1], scales.shape[0]
+    if a.dtype != scales.dtype:
+        raise RuntimeError("gptq_gemm_gidx_large: activations and scales must share a dtype")
+    if qweight.shape[0] * 8 != k or g_idx.numel() != k or tuple(qzeros.shape) != (groups, n // 8) or scales.shape[1] != n:
+        raise RuntimeError("gptq_gemm_gidx_large: shape mismatch")
+    out = torch.empty((m, n), dtype=a.dtype, device=a.device)
+    if m == 0:
+        return out
+    if not gptq_gidx_large_ok(m, n, k, groups, a.dtype):
+        raise RuntimeError(f"gptq_gemm_gidx_large: M={m} N={n} K={k} groups={groups} {a.dtype} is not served by the kernel")
+    if a.stride(1) != 1 or a.stride(0) % 8 != 0 or a.data_ptr() % 16 != 0:
+        a = a.contiguous()
+    g_idx = g_idx.to(torch.int32).contiguous()
+    qweight, qzeros, scales = qweight.contiguous(), qzeros.contiguous(), scales.contiguous()
+    lib = _lib.lib()
+    nbytes = lib.aphro_gptq_gemm_gidx_large_workspace_bytes(m, n, k, groups, _dt(a))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=a.device)        # (the caching allocator: capturable)
+    check(lib.aphro_gptq_gemm_gidx_large(a.data_ptr(), a.stride(0), qweight.data_ptr(), qzeros.data_ptr(), scales.data_ptr(),
+                                         g_idx.data_ptr(), out.data_ptr(), ws.data_ptr(), nbytes, m, n, k, groups,
+                                         zero_offset, _dt(a), _stream()), "gptq_gemm_gidx_large")
+    return out
+
+
 def gptq_gemm(a: torch.Tensor, b_q_weight: torch.Tensor,
               b_gptq_qzeros: torch.Tensor, b_gptq_scales: torch.Tensor,
               b_g_idx: torch.Tensor, use_exllama: bool, bit: int) -> torch.Tensor:
@@ -742,6 +787,10 @@ def gptq_gemm(a: torch.Tensor, b_q_weight: torch.Tensor,
     if not use_exllama and b_g_idx is not None and b_g_idx.numel() > 0 and 0 < m <= GPTQ_GIDX_MAX_M and \
             gptq_gidx_ok(m, b_q_weight.shape[1], a.shape[1], b_gptq_scales.shape[0], a.dtype):
         return gptq_gemm_gidx(a, b_q_weight, b_gptq_qzeros, b_gptq_scales, b_g_idx, 1)
+    if not use_exllama and b_g_idx is not None and b_g_idx.numel() > 0 and \
+            GPTQ_GIDX_LARGE_MIN_M <= m <= GPTQ_GIDX_LARGE_MAX_M and \
+            gptq_gidx_large_ok(m, b_q_weight.shape[1], a.shape[1], b_gptq_scales.shape[0], a.dtype):
+        return gptq_gemm_gidx_large(a, b_q_weight, b_gptq_qzeros, b_gptq_scales, b_g_idx, 1)
     large = use_exllama and wna16_large_ok(m, b_q_weight.shape[1], a.shape[1], b_gptq_scales.shape[0]) \
         and wna16_prefers_large(m, b_q_weight.shape[1], a.shape[1]) and not switch("APHRO_WNA16_NO_LARGE")
     if not use_exllama or (m >= GPTQ_DEQUANT_MIN_M and not large):

@@ -135,6 +135,9 @@ SIGNATURES = {
     "aphro_gptq_gemm_gidx_supported": (I, [L, L, L, L, I]),
     "aphro_gptq_gemm_gidx_workspace_bytes": (Z, [L, L, L]),
     "aphro_gptq_gemm_gidx": (I, [P, L, P, P, P, P, P, P, Z, L, L, L, L, I, I, P]),
+    "aphro_gptq_gemm_gidx_large_supported": (I, [L, L, L, L, I]),
+    "aphro_gptq_gemm_gidx_large_workspace_bytes": (Z, [L, L, L, L, I]),
+    "aphro_gptq_gemm_gidx_large": (I, [P, L, P, P, P, P, P, P, Z, L, L, L, L, I, I, P]),
     "aphro_lm_head_argmax": (I, [P, L, P, L, P, L, P, L, L, L, I, P]),
     "aphro_wna16_gemm_rowmajor": (I, [P, L, P, P, P, P, P, Z, L, L, L, L, I, I, I, P]),
     "aphro_convert_fp8": (I, [P, P, L, F, I, I, I, P]),

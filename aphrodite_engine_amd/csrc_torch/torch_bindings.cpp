@@ -50,8 +50,8 @@ torch::Tensor gptq_gemm(torch::Tensor a, torch::Tensor b_q_weight, torch::Tensor
   const int64_t groups = b_gptq_scales.size(0);
   if (!use_exllama) {
     // checkpoint order, groups through g_idx (act-order shards under row-parallel TP: `groups` is that of the unsharded
-    // matrix, no relation to K): csrc/gptq_gidx_gemm.hip up to GIDX_MAX_M rows (the Python op's GPTQ_GIDX_MAX_M), else the
-    // weight reconstructed once + a library GEMM (q_gemm.cu:1529-1544)
+    // matrix, no relation to K): csrc/gptq_gidx_gemm.hip up to GIDX_MAX_M rows (the Python op's GPTQ_GIDX_MAX_M),
+    // csrc/gptq_gidx_gemm_large.hip above it up to GPTQ_GIDX_LARGE_MAX_M rows, else the weight reconstructed once + a library GEMM (q_gemm.cu:1529-1544)
     constexpr int64_t GIDX_MAX_M = 64;
     TORCH_CHECK(groups > 0 && b_q_weight.size(0) * 8 == k, "gptq_gemm: q_weight [K/8, N] and scales [groups, N] expected");
     const int dt = act_dtype(a);
@@ -69,6 +69,19 @@ torch::Tensor gptq_gemm(torch::Tensor a, torch::Tensor b_q_weight, torch::Tensor
                                 groups, 1, dt, cur_stream()),
            "gptq_gemm");
       }
+      return out;
+    }
+    // prompt sizes: csrc/gptq_gidx_gemm_large.hip at GPTQ_GIDX_LARGE_MIN_M .. GPTQ_GIDX_LARGE_MAX_M rows (the Python op's
+    // constants of the same names: the two must agree; measured, profiles/gptq_gidx_gemm_large.txt)
+    constexpr int64_t GPTQ_GIDX_LARGE_MIN_M = 65, GPTQ_GIDX_LARGE_MAX_M = 136;
+    if (act_order && m >= GPTQ_GIDX_LARGE_MIN_M && m <= GPTQ_GIDX_LARGE_MAX_M && aphro_gptq_gemm_gidx_large_supported(m, n, k, groups, dt)) {
+      TORCH_CHECK(gi.numel() == k, "gptq_gemm: g_idx must have K entries");
+      torch::Tensor x = (a.stride(0) % 8 != 0 || ((uintptr_t)a.data_ptr() % 16) != 0) ? a.contiguous() : a;
+      auto wsl = torch::empty({(int64_t)aphro_gptq_gemm_gidx_large_workspace_bytes(m, n, k, groups, dt)}, a.options().dtype(torch::kUInt8));
+      ok(aphro_gptq_gemm_gidx_large(x.data_ptr(), x.stride(0), (const uint32_t*)b_q_weight.data_ptr(),
+                                    (const uint32_t*)b_gptq_qzeros.data_ptr(), b_gptq_scales.data_ptr(), (const int32_t*)gi.data_ptr(),
+                                    out.data_ptr(), wsl.data_ptr(), (size_t)wsl.numel(), m, n, k, groups, 1, dt, cur_stream()),
+         "gptq_gemm");
       return out;
     }
     TORCH_CHECK(act_order || k % groups == 0, "gptq_gemm: without g_idx the groups must divide K (groups=", groups, ", K=", k, ")");

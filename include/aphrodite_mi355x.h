@@ -915,6 +915,24 @@ int aphro_gptq_gemm_gidx(const void* a, int64_t lda, const uint32_t* q_weight, c
                          const int32_t* g_idx, void* c, void* workspace, size_t workspace_bytes, int64_t M, int64_t N,
                          int64_t K, int64_t groups, int zero_offset, int dtype, void* stream);
 
+/* The same checkpoint-order form (use_exllama = false, bit = 4, groups through g_idx) at PROMPT sizes (M > 64): the role
+ * of reconstruct + hipBLAS in `_C::gptq_gemm` (q_gemm.cu:1529-1544).  csrc/gptq_gidx_gemm_large.hip.  Tensors and
+ * arithmetic as aphro_gptq_gemm_gidx (f16 weights with the bits of aphro_gptq_dequant, g_idx clamped to [0, groups),
+ * bf16 activations widened to f16 with saturation into the workspace, scales converted to f16, fp32 accumulation, one
+ * rounding of the sum); a, q_weight, scales and c 16-byte aligned, lda % 8 == 0, lda >= K.  Any M >= 1 in one call.  Small
+ * grids cut K into slices whose fp32 slabs (workspace) are added in slice order by a second launch: deterministic, no
+ * flags, tickets or atomics -- replays under a HIP graph.
+ * aphro_gptq_gemm_gidx_large_supported: 1 exactly when the kernel takes the shape -- f16 | bf16, M >= 1, N % 128 == 0,
+ * K % 32 == 0, 1 <= groups <= 232 (the scale / zero table of a 128-column tile holds every group in LDS), and a,
+ * q_weight and c each below 4 GiB.
+ * aphro_gptq_gemm_gidx_large_workspace_bytes: the f16 copy of bf16 activations + the fp32 slabs of the plan for the shape
+ * (0 for an unsupported shape); workspace 16-byte aligned, APHRO_ERR_WORKSPACE without a launch when it is too small. */
+int aphro_gptq_gemm_gidx_large_supported(int64_t M, int64_t N, int64_t K, int64_t groups, int dtype);
+size_t aphro_gptq_gemm_gidx_large_workspace_bytes(int64_t M, int64_t N, int64_t K, int64_t groups, int dtype);
+int aphro_gptq_gemm_gidx_large(const void* a, int64_t lda, const uint32_t* q_weight, const uint32_t* qzeros,
+                               const void* scales, const int32_t* g_idx, void* c, void* workspace, size_t workspace_bytes,
+                               int64_t M, int64_t N, int64_t K, int64_t groups, int zero_offset, int dtype, void* stream);
+
 /* FP8 W8A8 decode GEMM for M <= 32, one workgroup per CU on a strip-major copy of the weight (round 4,
  * csrc/fp8_gemm_resident.hip): same role and arithmetic as aphro_scaled_mm_fp8 / aphro_scaled_mm_fp8_slabs
  * (cutlass_scaled_mm, kernels/quantization/cutlass_w8a8/scaled_mm_entry.cu:92-137; torch._scaled_mm on ROCm,
