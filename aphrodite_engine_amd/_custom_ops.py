@@ -144,7 +144,7 @@ def _require_cuda(*ts):
 def _paged_attention(out, exp_sums, max_logits, tmp_out, query, key_cache,
                      value_cache, num_kv_heads, scale, block_tables, seq_lens,
                      block_size, max_seq_len, alibi_slopes, kv_cache_dtype,
-                     k_scale, v_scale, partition_size):
+                     k_scale, v_scale, partition_size, softcap: float = 0.0):
     _require_cuda(out, query, key_cache, value_cache, block_tables, seq_lens)
     num_seqs, num_heads, head_size = query.shape
     if query.stride(2) != 1 or query.stride(1) != head_size:
@@ -155,6 +155,17 @@ def _paged_attention(out, exp_sums, max_logits, tmp_out, query, key_cache,
         raise RuntimeError("block_tables / seq_lens must be int32")
     if alibi_slopes is not None and alibi_slopes.dtype != torch.float32:
         alibi_slopes = alibi_slopes.float()
+    if softcap:   # logit soft cap: the decode kernel's capped variant (head 128 / 256; anything else is refused there)
+        check(_lib.lib().aphro_paged_attention_softcap(
+            out.data_ptr(), _ptr(exp_sums), _ptr(max_logits), _ptr(tmp_out),
+            query.data_ptr(), key_cache.data_ptr(), value_cache.data_ptr(),
+            num_seqs, num_heads, num_kv_heads, head_size, float(scale),
+            block_tables.data_ptr(), seq_lens.data_ptr(), block_tables.stride(0),
+            block_size, int(max_seq_len), _ptr(alibi_slopes), query.stride(0),
+            key_cache.stride(0), key_cache.stride(1), _dt(query), _kv(kv_cache_dtype),
+            float(k_scale), float(v_scale), partition_size, float(softcap), _stream()),
+            "paged_attention")
+        return
     check(_lib.lib().aphro_paged_attention(
         out.data_ptr(), _ptr(exp_sums), _ptr(max_logits), _ptr(tmp_out),
         query.data_ptr(), key_cache.data_ptr(), value_cache.data_ptr(),
@@ -172,12 +183,13 @@ def paged_attention_v1(out, query, key_cache, value_cache, num_kv_heads, scale,
                        tp_rank: int = 0, blocksparse_local_blocks: int = 0,
                        blocksparse_vert_stride: int = 0,
                        blocksparse_block_size: int = 64,
-                       blocksparse_head_sliding_step: int = 0) -> None:
+                       blocksparse_head_sliding_step: int = 0, softcap: float = 0.0) -> None:
+    """``softcap`` (ours; flash-attention's name): logit = softcap * tanh(scale * q.k / softcap), 0 = off."""
     if blocksparse_vert_stride > 1:
         raise RuntimeError("blocksparse attention is out of scope (SURVEY 2.1)")
     _paged_attention(out, None, None, None, query, key_cache, value_cache,
                      num_kv_heads, scale, block_tables, seq_lens, block_size,
-                     max_seq_len, alibi_slopes, kv_cache_dtype, k_scale, v_scale, 0)
+                     max_seq_len, alibi_slopes, kv_cache_dtype, k_scale, v_scale, 0, softcap)
 
 
 def paged_attention_v2(out, exp_sum, max_logits, tmp_out, query, key_cache,
@@ -187,20 +199,20 @@ def paged_attention_v2(out, exp_sum, max_logits, tmp_out, query, key_cache,
                        blocksparse_local_blocks: int = 0,
                        blocksparse_vert_stride: int = 0,
                        blocksparse_block_size: int = 64,
-                       blocksparse_head_sliding_step: int = 0) -> None:
+                       blocksparse_head_sliding_step: int = 0, softcap: float = 0.0) -> None:
     if blocksparse_vert_stride > 1:
         raise RuntimeError("blocksparse attention is out of scope (SURVEY 2.1)")
     part = _partition_size(tmp_out, max_seq_len)
     _paged_attention(out, exp_sum, max_logits, tmp_out, query, key_cache,
                      value_cache, num_kv_heads, scale, block_tables, seq_lens,
                      block_size, max_seq_len, alibi_slopes, kv_cache_dtype,
-                     k_scale, v_scale, part)
+                     k_scale, v_scale, part, softcap)
 
 
 def paged_attention_rocm(out, exp_sum, max_logits, tmp_out, query, key_cache,
                          value_cache, num_kv_heads, scale, block_tables,
                          seq_lens, block_size, max_seq_len, alibi_slopes,
-                         kv_cache_dtype, k_scale, v_scale) -> None:
+                         kv_cache_dtype, k_scale, v_scale, softcap: float = 0.0) -> None:
     """`_rocm_C::paged_attention` (kernels/rocm/torch_bindings.cpp): the reference's ROCm backend calls it for every decode
     batch on gfx9 (rocm_flash_attn.py:539-560, 633-641) with scratch for 512-token partitions.  Only ``out`` is read back by
     the caller; where one launch over whole sequences is the faster form -- the reference's own v1 / v2 rule,
@@ -215,7 +227,7 @@ def paged_attention_rocm(out, exp_sum, max_logits, tmp_out, query, key_cache,
     _paged_attention(out, exp_sum, max_logits, tmp_out, query, key_cache,
                      value_cache, num_kv_heads, scale, block_tables, seq_lens,
                      block_size, max_seq_len, alibi_slopes, kv_cache_dtype,
-                     k_scale, v_scale, part)
+                     k_scale, v_scale, part, softcap)
 
 
 def _partition_size(tmp_out: torch.Tensor, max_seq_len: int) -> int:
@@ -236,12 +248,14 @@ def flash_attn_varlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                       cu_seqlens: torch.Tensor, max_seqlen: int, softmax_scale: float,
                       causal: bool = True,
                       alibi_slopes: Optional[torch.Tensor] = None,
-                      window_size: Optional[tuple] = None) -> torch.Tensor:
+                      window_size: Optional[tuple] = None, softcap: float = 0.0) -> torch.Tensor:
     """Prefill self-attention over packed sequences: the role of
     triton_attention / flash_attn_varlen_func in ROCmFlashAttentionImpl
     (rocm_flash_attn.py:455-508).  q [T,Hq,hd], k/v [T,Hkv,hd] (token-strided
     views allowed), cu_seqlens int32 [B+1]; returns [T,Hq,hd].  ``window_size`` = flash_attn_varlen_func's (left, right)
-    (rocm_flash_attn.py:506; (-1, -1) / None = off): under causal attention query i sees keys i - left .. i."""
+    (rocm_flash_attn.py:506; (-1, -1) / None = off): under causal attention query i sees keys i - left .. i.
+    ``softcap`` (flash_attn_varlen_func's name; 0 = off): logit = softcap * tanh(softmax_scale * q.k / softcap), head sizes
+    128 / 256."""
     _require_cuda(q, k, v, cu_seqlens)
     t, hq, hd = q.shape
     hkv = k.shape[1]
@@ -254,9 +268,17 @@ def flash_attn_varlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     if alibi_slopes is not None and alibi_slopes.dtype != torch.float32:
         alibi_slopes = alibi_slopes.float()
     left = int(window_size[0]) if window_size is not None else -1
+    if left >= 0 and not causal:
+        raise RuntimeError("flash_attn_varlen: a sliding window needs causal attention")
+    if softcap:
+        check(_lib.lib().aphro_flash_attn_varlen_softcap(
+            out.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
+            cu_seqlens.data_ptr(), cu_seqlens.numel() - 1, int(max_seqlen), hq, hkv, hd,
+            q.stride(0), k.stride(0), v.stride(0), float(softmax_scale),
+            1 if causal else 0, _ptr(alibi_slopes), left + 1 if left >= 0 else 0, float(softcap), _dt(q), _stream()),
+            "flash_attn_varlen")
+        return out
     if left >= 0:
-        if not causal:
-            raise RuntimeError("flash_attn_varlen: a sliding window needs causal attention")
         check(_lib.lib().aphro_flash_attn_varlen_window(
             out.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
             cu_seqlens.data_ptr(), cu_seqlens.numel() - 1, int(max_seqlen), hq, hkv, hd,
@@ -283,13 +305,15 @@ def context_attention_fwd(q, k, v, o, kv_cache_dtype: str, k_cache, v_cache, b_l
                           b_seq_len, b_ctx_len, max_input_len: int, k_scale: float = 1.0,
                           v_scale: float = 1.0, alibi_slopes: Optional[torch.Tensor] = None,
                           sliding_window: Optional[int] = None, max_seq_len: Optional[int] = None,
-                          total_kv_tokens: Optional[int] = None) -> None:
+                          total_kv_tokens: Optional[int] = None, scale: Optional[float] = None,
+                          softcap: float = 0.0) -> None:
     """attention/ops/prefix_prefill.py:696-711 (same argument order; ``max_seq_len`` / ``total_kv_tokens`` are optional
     host-side hints -- max and sum of ``b_seq_len`` -- that save a device sync on the long-prompt path).  q/k/v/o [T,H,hd]
     views of the new tokens; k_cache [NB,Hkv,hd/x,block,x], v_cache [NB,Hkv,hd,block];
     b_loc = block tables, b_start_loc = query_start_loc [B+1], b_seq_len = context + new,
     b_ctx_len = cached context.  Like the reference the softmax scale is 1/sqrt(hd)
-    (prefix_prefill.py:745)."""
+    (prefix_prefill.py:745) unless ``scale`` is given.  ``softcap`` (0 = off): logit soft cap, head sizes 128 / 256, on the
+    gathered path with the caller's ``scale`` (Gemma-2 27B's is not 1/sqrt(hd))."""
     _require_cuda(q, k, v, o, k_cache, v_cache, b_loc, b_start_loc, b_seq_len, b_ctx_len)
     if q.dtype not in (torch.float16, torch.bfloat16):
         raise RuntimeError("context_attention_fwd: query must be fp16 or bf16")
@@ -306,6 +330,23 @@ def context_attention_fwd(q, k, v, o, kv_cache_dtype: str, k_cache, v_cache, b_l
         slopes = alibi_slopes.to(device=q.device, dtype=torch.float32).contiguous()
     win = int(sliding_window) if sliding_window is not None and sliding_window > 0 else 0
     lib = _lib.lib()
+    sm_scale = head_size ** -0.5 if scale is None else float(scale)
+    if softcap:
+        if head_size not in (128, 256):
+            raise RuntimeError(f"context_attention_fwd: a logit soft cap is served for head_size 128 / 256 only (got {head_size})")
+        if max_seq_len is not None and total_kv_tokens is not None:
+            msl, tot = int(max_seq_len), int(total_kv_tokens)
+        else:
+            msl, tot = int(b_seq_len.max().item()), int(b_seq_len.sum().item())
+        ws = _workspace(q.device, lib.aphro_context_attention_workspace_bytes(tot, batch, k.shape[1], head_size))
+        check(lib.aphro_context_attention_gathered_softcap(
+            o.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+            b_loc.data_ptr(), b_start_loc.data_ptr(), b_seq_len.data_ptr(), b_ctx_len.data_ptr(), batch,
+            int(max_input_len), msl, tot, b_loc.shape[1], q.shape[1], k.shape[1], head_size, v_cache.shape[3],
+            k_cache.shape[4], q.stride(0), k.stride(0), v.stride(0), o.stride(0), sm_scale,
+            float(k_scale), float(v_scale), _ptr(slopes), win, float(softcap), _dt(q), _kv(kv_cache_dtype), ws.data_ptr(),
+            ws.numel(), _stream()), "context_attention_fwd")
+        return
     if head_size in (64, 96, 128, 256) and not switch("APHRO_CA_NO_GATHER"):
         # gather the cached context once, then the prefill tile machines over context + new tokens (every head size, ALiBi,
         # sliding window: round 3).  The caller passes the host-side maxima when it has them (the attention metadata does);
@@ -324,7 +365,7 @@ def context_attention_fwd(q, k, v, o, kv_cache_dtype: str, k_cache, v_cache, b_l
             o.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
             b_loc.data_ptr(), b_start_loc.data_ptr(), b_seq_len.data_ptr(), b_ctx_len.data_ptr(), batch,
             int(max_input_len), msl, tot, b_loc.shape[1], q.shape[1], k.shape[1], head_size, v_cache.shape[3],
-            k_cache.shape[4], q.stride(0), k.stride(0), v.stride(0), o.stride(0), head_size ** -0.5,
+            k_cache.shape[4], q.stride(0), k.stride(0), v.stride(0), o.stride(0), sm_scale,
             float(k_scale), float(v_scale), _ptr(slopes), win, _dt(q), _kv(kv_cache_dtype), ws.data_ptr(), ws.numel(),
             _stream()), "context_attention_fwd")
         return
@@ -333,7 +374,7 @@ def context_attention_fwd(q, k, v, o, kv_cache_dtype: str, k_cache, v_cache, b_l
         o.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
         b_loc.data_ptr(), b_start_loc.data_ptr(), b_seq_len.data_ptr(), b_ctx_len.data_ptr(), batch,
         int(max_input_len), b_loc.shape[1], q.shape[1], k.shape[1], head_size, v_cache.shape[3],
-        k_cache.shape[4], q.stride(0), k.stride(0), v.stride(0), o.stride(0), head_size ** -0.5,
+        k_cache.shape[4], q.stride(0), k.stride(0), v.stride(0), o.stride(0), sm_scale,
         float(k_scale), float(v_scale), _ptr(slopes), win, _dt(q), _kv(kv_cache_dtype), _stream()),
         "context_attention_fwd")
 

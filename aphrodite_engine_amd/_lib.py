@@ -143,6 +143,8 @@ SIGNATURES = {
     "aphro_convert_fp8": (I, [P, P, L, F, I, I, I, P]),
     "aphro_paged_attention": (I, [P, P, P, P, P, P, P, I, I, I, I, F, P, P, I, I, I, P,
                                   L, L, L, I, I, F, F, I, P]),
+    "aphro_paged_attention_softcap": (I, [P, P, P, P, P, P, P, I, I, I, I, F, P, P, I, I, I, P,
+                                          L, L, L, I, I, F, F, I, F, P]),
     "aphro_static_scaled_fp8_quant": (I, [P, P, P, L, L, I, P]),
     "aphro_dynamic_scaled_fp8_quant": (I, [P, P, P, L, L, I, P]),
     "aphro_dynamic_scaled_fp8_quant_ws": (I, [P, P, P, P, Z, L, L, I, P]),
@@ -161,6 +163,7 @@ SIGNATURES = {
     "aphro_rotary_embedding": (I, [P, P, P, L, I, I, I, I, P, L, L, I, I, P]),
     "aphro_flash_attn_varlen": (I, [P, P, P, P, P, I, I, I, I, I, L, L, L, F, I, P, I, P]),
     "aphro_flash_attn_varlen_window": (I, [P, P, P, P, P, I, I, I, I, I, L, L, L, F, I, P, I, I, P]),
+    "aphro_flash_attn_varlen_softcap": (I, [P, P, P, P, P, I, I, I, I, I, L, L, L, F, I, P, I, F, I, P]),
     "aphro_context_attention": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, L, L, L, L,
                                     F, F, F, P, I, I, I, P]),
     "aphro_context_attention_workspace_bytes": (Z, [L, I, I, I]),
@@ -169,6 +172,9 @@ SIGNATURES = {
     # workspace bytes stream   (round 3: sliding_window before dtype)
     "aphro_context_attention_gathered": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, L, I, I, I, I, I, I, L, L, L, L,
                                              F, F, F, P, I, I, I, P, Z, P]),
+    # ... sliding_window, softcap before dtype
+    "aphro_context_attention_gathered_softcap": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, L, I, I, I, I, I, I, L, L, L, L,
+                                                     F, F, F, P, I, F, I, I, P, Z, P]),
 }
 
 OK = 0

@@ -155,8 +155,11 @@ class MI355XAttentionImpl:
                  blocksparse_params=None, logits_soft_cap: Optional[float] = None) -> None:
         if blocksparse_params is not None:
             raise ValueError("MI355X backend does not support blocksparse attention.")
-        if logits_soft_cap is not None:
-            raise ValueError("MI355X backend does not support attention logits soft capping.")
+        # attention/layer.py hands every backend the model's cap (Gemma-2: 50.0); None / 0 = off.  Served by the capped
+        # variants of the decode and prefill kernels, head sizes 128 / 256 (the ops refuse the rest).
+        self.logits_soft_cap = float(logits_soft_cap) if logits_soft_cap else 0.0
+        if self.logits_soft_cap < 0:
+            raise ValueError("logits_soft_cap must be positive.")
         self.num_heads = num_heads
         self.head_size = head_size
         self.scale = float(scale)
@@ -226,12 +229,14 @@ class MI355XAttentionImpl:
                     prefill_meta.max_query_len, self.alibi_slopes, self.sliding_window[0],
                     k_scale, v_scale,
                     # host-side maxima of the prefill sequences (seq_lens is a Python list): no .item() per layer
-                    max_seq_len=max(prefill_meta.seq_lens), total_kv_tokens=sum(prefill_meta.seq_lens))
+                    max_seq_len=max(prefill_meta.seq_lens), total_kv_tokens=sum(prefill_meta.seq_lens),
+                    # a capped layer's scale is the model's (Gemma-2 27B: not 1/sqrt(hd)); uncapped: the reference's rule
+                    scale=self.scale if self.logits_soft_cap else None, softcap=self.logits_soft_cap)
             else:
                 out = ops.flash_attn_varlen(
                     query, key, value, prefill_meta.seq_start_loc,
                     prefill_meta.max_prefill_seq_len, self.scale, causal=True,
-                    alibi_slopes=self.alibi_slopes, window_size=self.sliding_window)
+                    alibi_slopes=self.alibi_slopes, window_size=self.sliding_window, softcap=self.logits_soft_cap)
                 output[:num_prefill_tokens] = out
 
         if decode_meta := attn_metadata.decode_metadata:
@@ -251,7 +256,8 @@ class MI355XAttentionImpl:
                 output[num_prefill_tokens:], exp_sums, max_logits, tmp_output,
                 decode_query, key_cache, value_cache, self.num_kv_heads, self.scale,
                 decode_meta.block_tables, decode_meta.seq_lens_tensor, block_size,
-                max_seq_len, self.alibi_slopes, self.kv_cache_dtype, k_scale, v_scale)
+                max_seq_len, self.alibi_slopes, self.kv_cache_dtype, k_scale, v_scale,
+                softcap=self.logits_soft_cap)
         return output.view(num_tokens, hidden_size)
 
 

@@ -231,6 +231,16 @@ __device__ __forceinline__ void rope_pair(float x, float y, float c, float s, fl
   yo = yc + xs;
 }
 
+// Attention logit soft cap (Gemma-2) straight off the raw q.k accumulator: returns cap * tanh(s * scale / cap), with
+// tanh(x) = 1 - 2 / (1 + exp2(2 log2(e) x)).  The caller folds everything it can into the two constants:
+//   k   = scale * 2 log2(e) / cap   (the multiply that used to be `s * scale`)
+//   cap = the cap in the domain the caller's softmax runs in (natural: cap ; log2: cap * log2(e))
+// v_mul, v_exp_f32, v_add, v_rcp_f32, v_fma.  Saturation needs no clamp: exp2 -> inf gives rcp 0 -> +cap, exp2 -> 0 gives
+// rcp 1 -> -cap.  The cancellation around s = 0 is an absolute error of ~2^-23 cap: no polynomial.
+__device__ __forceinline__ float softcap_logit(float s, float k, float cap) {
+  return __builtin_fmaf(__builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(s * k)), -2.f * cap, cap);
+}
+
 // ---- wave reductions ------------------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -43,7 +43,10 @@ constexpr int FA_VT_STRIDE = 36;  // halfs per V^T row (32 + 4 pad)
 
 // QT = 16-row query tiles per wave: every K / V^T fragment read from LDS (and every byte staged
 // into it) is used by QT MFMAs -- the staging path, not the MFMA pipe, bounds this kernel.
-template <typename T, int HD, int QT>
+// CAP: logit soft cap (Gemma-2), a separate instantiation -- logit = cap * tanh(scale * q.k / cap), then ALiBi, then the
+// mask.  In the log2 domain the whole cap is softcap_logit (common.h) with k = scale * 2 log2e / cap and cap * log2e: the
+// multiply by sc2 it replaces, plus v_exp_f32 / v_add / v_rcp_f32 / v_fma per score, between the QK and the PV MFMAs.
+template <typename T, int HD, int QT, bool CAP = false>
 __global__ __launch_bounds__(256) void flash_attn_varlen_kernel(FAParams p) {
   constexpr int NCH = HD / 8;    // 16-byte chunks per row
   constexpr int SWZ = (NCH & -NCH) - 1;  // XOR mask: largest power of two dividing NCH, minus 1
@@ -87,7 +90,9 @@ __global__ __launch_bounds__(256) void flash_attn_varlen_kernel(FAParams p) {
     for (int ks = 0; ks < NKS; ++ks) qf[t][ks] = *reinterpret_cast<const u32x4*>(qp + 32 * ks + 8 * g);
   }
   const float slope = p.alibi ? p.alibi[head] : 0.f;
-  const float sc2 = p.scale * 1.44269504088896f;     // softmax in the log2 domain
+  // softmax in the log2 domain; capped form: sc2 = the argument scale of softcap_logit, cap2 = the cap in that domain
+  const float sc2 = CAP ? p.scale * (2.f * 1.44269504088896f) / p.softcap : p.scale * 1.44269504088896f;
+  const float cap2 = p.softcap * 1.44269504088896f;
   const float slope2 = slope * 1.44269504088896f;
 
   f32x4 o[QT][NDT];
@@ -156,7 +161,9 @@ __global__ __launch_bounds__(256) void flash_attn_varlen_kernel(FAParams p) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               const int tok = t0 + 16 * h + 4 * g + r;
-              float x = s[t][h][r] * sc2 + slope2 * (float)(tok - qrow[t] - off);
+              float x;
+              if constexpr (CAP) x = softcap_logit(s[t][h][r], sc2, cap2) + slope2 * (float)(tok - qrow[t] - off);
+              else x = s[t][h][r] * sc2 + slope2 * (float)(tok - qrow[t] - off);
               const bool ok = tok < len && (!p.causal || tok <= qrow[t] + off) && (win <= 0 || tok > qrow[t] + off - win);
               x = ok ? x : -1e30f;
               pv[h][r] = x;
@@ -167,7 +174,8 @@ __global__ __launch_bounds__(256) void flash_attn_varlen_kernel(FAParams p) {
           for (int h = 0; h < 2; ++h)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-              pv[h][r] = s[t][h][r] * sc2;
+              if constexpr (CAP) pv[h][r] = softcap_logit(s[t][h][r], sc2, cap2);
+              else pv[h][r] = s[t][h][r] * sc2;
               mx = __builtin_fmaxf(mx, pv[h][r]);
             }
         }
@@ -241,7 +249,7 @@ __global__ __launch_bounds__(256) void flash_attn_varlen_kernel(FAParams p) {
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 constexpr int FA2_BN = 64;
 
-template <typename T, int HD, int QT, int NWV>
+template <typename T, int HD, int QT, int NWV, bool CAP = false>
 __global__ __launch_bounds__(NWV * 64) void flash_attn_varlen_v2_kernel(FAParams p) {
   constexpr int NCH = HD / 8;
   constexpr int SWZ = (NCH & -NCH) - 1;
@@ -285,7 +293,8 @@ __global__ __launch_bounds__(NWV * 64) void flash_attn_varlen_v2_kernel(FAParams
     for (int ks = 0; ks < NKS; ++ks) qf[t][ks] = *reinterpret_cast<const u32x4*>(qp + 32 * ks + 8 * g);
   }
   const float slope = p.alibi ? p.alibi[head] : 0.f;
-  const float sc2 = p.scale * 1.44269504088896f;
+  const float sc2 = CAP ? p.scale * (2.f * 1.44269504088896f) / p.softcap : p.scale * 1.44269504088896f;   // (see the first generation)
+  const float cap2 = p.softcap * 1.44269504088896f;
   const float slope2 = slope * 1.44269504088896f;
 
   f32x4 o[QT][NDT];
@@ -371,7 +380,9 @@ __global__ __launch_bounds__(NWV * 64) void flash_attn_varlen_v2_kernel(FAParams
 #pragma unroll
               for (int r = 0; r < 4; ++r) {
                 const int tok = tb + 16 * h + 4 * g + r;
-                float x = s[t][h][r] * sc2 + slope2 * (float)(tok - qrow[t] - off);
+                float x;
+                if constexpr (CAP) x = softcap_logit(s[t][h][r], sc2, cap2) + slope2 * (float)(tok - qrow[t] - off);
+                else x = s[t][h][r] * sc2 + slope2 * (float)(tok - qrow[t] - off);
                 const bool ok = tok < len && (!p.causal || tok <= qrow[t] + off) && (win <= 0 || tok > qrow[t] + off - win);
                 x = ok ? x : -1e30f;
                 pv[h][r] = x;
@@ -382,7 +393,8 @@ __global__ __launch_bounds__(NWV * 64) void flash_attn_varlen_v2_kernel(FAParams
             for (int h = 0; h < 2; ++h)
 #pragma unroll
               for (int r = 0; r < 4; ++r) {
-                pv[h][r] = s[t][h][r] * sc2;
+                if constexpr (CAP) pv[h][r] = softcap_logit(s[t][h][r], sc2, cap2);
+                else pv[h][r] = s[t][h][r] * sc2;
                 mx = __builtin_fmaxf(mx, pv[h][r]);
               }
           }
@@ -1101,10 +1113,37 @@ extern "C" int aphro_context_attention(void* out, const void* q, const void* k, 
 }
 
 
+// Capped calls (FAParams::softcap > 0): the CAP instantiations of the first / second generation tile machines, head 128 and
+// 256 (the entry points refuse the rest), with or without a window or a key offset.  Same tile-shape rule as below: the
+// second generation's 128-row workgroups once the queries are long enough, head 256 on the first generation (its K + V
+// tile does not fit the second's static LDS).  Long head-128 prompts without a window: the fourth generation's capped form
+// (flash_attn_v4.hip), which beats the capped second generation from 1100 keys up (profiles/attn_softcap.txt).
+static int fa_dispatch_softcap(FAParams p, int head_size, int dtype, int batch, int max_query_len, int max_key_len, hipStream_t st) {
+  // long prompts without a window (Gemma-2's global layers): the fourth generation's capped form, same threshold knob
+  if (head_size == 128 && p.window <= 0 && max_key_len >= 1024 && max_key_len >= knobs().fa_v4_min_keys) {
+    p.nqt_max = (max_query_len + 255) / 256;
+    p.xcd_remap = (batch * p.num_kv_heads) % 8 == 0 && !knobs().fa_no_xcd;
+    return fa_v4_launch(p, dtype, batch, st);
+  }
+  p.nqt_max = 0; p.xcd_remap = 0;
+  const bool offset_keys = p.cu_seqlens_k != nullptr;
+  const bool v2 = head_size == 128 && (max_query_len >= 512 || (offset_keys && max_query_len >= 128));
+  const int bm = v2 ? 128 : 64;
+  dim3 grid((unsigned)((max_query_len + bm - 1) / bm), (unsigned)p.num_heads, (unsigned)batch);
+#define FA_CAP_L(TT) { if (v2) hipLaunchKernelGGL((flash_attn_varlen_v2_kernel<TT, 128, 2, 4, true>), grid, dim3(256), 0, st, p); \
+                       else if (head_size == 128) hipLaunchKernelGGL((flash_attn_varlen_kernel<TT, 128, 1, true>), grid, dim3(256), 0, st, p); \
+                       else hipLaunchKernelGGL((flash_attn_varlen_kernel<TT, 256, 1, true>), grid, dim3(256), 0, st, p); }
+  if (dtype == APHRO_F16) FA_CAP_L(Half) else FA_CAP_L(BFloat)
+#undef FA_CAP_L
+  APHRO_LAUNCH_CHECK();
+  return APHRO_OK;
+}
+
 // One dispatcher for the three prefill kernel generations (p fully set up except nqt_max / xcd_remap): third generation
 // for head 128, sequences >= 1024, no sliding window; second for head 64 / 128 (always when the keys carry a context
 // offset: its 64-key tiles are what the gathered-context path wants); first generation for the rest.
 static int fa_dispatch(FAParams p, int head_size, int dtype, int batch, int max_query_len, int max_key_len, hipStream_t st) {
+  if (p.softcap > 0.f) return fa_dispatch_softcap(p, head_size, dtype, batch, max_query_len, max_key_len, st);
   if (head_size == 128 && max_key_len >= 1024 && p.window <= 0 && !APHRO_LAB_ENV_INT("APHRO_FA_NO_V3", 0)) {
     p.nqt_max = (max_query_len + 255) / 256;
     p.xcd_remap = (batch * p.num_kv_heads) % 8 == 0 && !knobs().fa_no_xcd;
@@ -1168,15 +1207,18 @@ extern "C" size_t aphro_context_attention_workspace_bytes(int64_t total_kv_token
 // prefill tile machines run over context + new tokens (third generation for head 128 / >= 1024 keys / no window, second
 // for head 64 / 128, first for the rest) -- round 3: the scalar-gather aphro_context_attention kernel is no longer on any
 // path the Python op takes.
-extern "C" int aphro_context_attention_gathered(void* out, const void* q, const void* k, const void* v, const void* k_cache,
-                                                const void* v_cache, const int32_t* block_tables, const int32_t* q_start_loc,
-                                                const int32_t* seq_lens, const int32_t* ctx_lens, int batch, int max_query_len,
-                                                int max_seq_len, int64_t total_kv_tokens, int max_blocks, int num_heads,
-                                                int num_kv_heads, int head_size, int block_size, int x, int64_t q_stride,
-                                                int64_t k_stride, int64_t v_stride, int64_t o_stride, float scale, float k_scale,
-                                                float v_scale, const float* alibi_slopes, int sliding_window, int dtype,
-                                                int kv_dtype, void* workspace, size_t workspace_bytes, void* stream) {
+static int context_attention_gathered_impl(void* out, const void* q, const void* k, const void* v, const void* k_cache,
+                                           const void* v_cache, const int32_t* block_tables, const int32_t* q_start_loc,
+                                           const int32_t* seq_lens, const int32_t* ctx_lens, int batch, int max_query_len,
+                                           int max_seq_len, int64_t total_kv_tokens, int max_blocks, int num_heads,
+                                           int num_kv_heads, int head_size, int block_size, int x, int64_t q_stride,
+                                           int64_t k_stride, int64_t v_stride, int64_t o_stride, float scale, float k_scale,
+                                           float v_scale, const float* alibi_slopes, int sliding_window, float softcap, int dtype,
+                                           int kv_dtype, void* workspace, size_t workspace_bytes, void* stream) {
   APHRO_CHECK(dtype == APHRO_F16 || dtype == APHRO_BF16, "context_attention: dtype must be f16 or bf16");
+  APHRO_CHECK(softcap >= 0.f && (softcap == 0.f || head_size == 128 || head_size == 256),
+              "context_attention_gathered: a logit soft cap (>= 0) is served for head_size 128 / 256 only; got softcap=%g head_size=%d",
+              (double)softcap, head_size);
   APHRO_CHECK(kv_dtype >= APHRO_KV_AUTO && kv_dtype <= APHRO_KV_FP8_E5M2, "Unsupported data type of kv cache: %d", kv_dtype);
   APHRO_CHECK(head_size == 64 || head_size == 96 || head_size == 128 || head_size == 256,
               "context_attention_gathered: head_size %d (64 / 96 / 128 / 256)", head_size);
@@ -1211,11 +1253,44 @@ extern "C" int aphro_context_attention_gathered(void* out, const void* q, const 
 #undef CG_L
   APHRO_LAUNCH_CHECK();
   FAParams p;
+  p.softcap = softcap;
   p.out = out; p.q = q; p.k = kc; p.v = vc; p.cu_seqlens = q_start_loc; p.cu_seqlens_k = cu_k; p.alibi = alibi_slopes;
   p.num_heads = num_heads; p.num_kv_heads = num_kv_heads;
   p.q_stride = q_stride; p.k_stride = (int64_t)num_kv_heads * head_size; p.v_stride = p.k_stride; p.o_stride = o_stride;
   p.scale = scale; p.causal = 1; p.window = sliding_window > 0 ? sliding_window : 0;
   return fa_dispatch(p, head_size, dtype, batch, max_query_len, max_seq_len, st);
+}
+
+extern "C" int aphro_context_attention_gathered(void* out, const void* q, const void* k, const void* v, const void* k_cache,
+                                                const void* v_cache, const int32_t* block_tables, const int32_t* q_start_loc,
+                                                const int32_t* seq_lens, const int32_t* ctx_lens, int batch, int max_query_len,
+                                                int max_seq_len, int64_t total_kv_tokens, int max_blocks, int num_heads,
+                                                int num_kv_heads, int head_size, int block_size, int x, int64_t q_stride,
+                                                int64_t k_stride, int64_t v_stride, int64_t o_stride, float scale, float k_scale,
+                                                float v_scale, const float* alibi_slopes, int sliding_window, int dtype,
+                                                int kv_dtype, void* workspace, size_t workspace_bytes, void* stream) {
+  return context_attention_gathered_impl(out, q, k, v, k_cache, v_cache, block_tables, q_start_loc, seq_lens, ctx_lens, batch,
+                                         max_query_len, max_seq_len, total_kv_tokens, max_blocks, num_heads, num_kv_heads,
+                                         head_size, block_size, x, q_stride, k_stride, v_stride, o_stride, scale, k_scale,
+                                         v_scale, alibi_slopes, sliding_window, 0.f, dtype, kv_dtype, workspace,
+                                         workspace_bytes, stream);
+}
+
+// ... with a logit soft cap: logit = softcap * tanh(scale * q.k / softcap) (the gathered keys are already dequantised, so
+// k_scale sits inside q.k), then ALiBi, then the mask.  `scale` is the caller's, as in the uncapped entry point.
+extern "C" int aphro_context_attention_gathered_softcap(void* out, const void* q, const void* k, const void* v, const void* k_cache,
+                                                        const void* v_cache, const int32_t* block_tables, const int32_t* q_start_loc,
+                                                        const int32_t* seq_lens, const int32_t* ctx_lens, int batch, int max_query_len,
+                                                        int max_seq_len, int64_t total_kv_tokens, int max_blocks, int num_heads,
+                                                        int num_kv_heads, int head_size, int block_size, int x, int64_t q_stride,
+                                                        int64_t k_stride, int64_t v_stride, int64_t o_stride, float scale, float k_scale,
+                                                        float v_scale, const float* alibi_slopes, int sliding_window, float softcap,
+                                                        int dtype, int kv_dtype, void* workspace, size_t workspace_bytes, void* stream) {
+  return context_attention_gathered_impl(out, q, k, v, k_cache, v_cache, block_tables, q_start_loc, seq_lens, ctx_lens, batch,
+                                         max_query_len, max_seq_len, total_kv_tokens, max_blocks, num_heads, num_kv_heads,
+                                         head_size, block_size, x, q_stride, k_stride, v_stride, o_stride, scale, k_scale,
+                                         v_scale, alibi_slopes, sliding_window, softcap, dtype, kv_dtype, workspace,
+                                         workspace_bytes, stream);
 }
 
 
@@ -1226,14 +1301,18 @@ static int fa_varlen_entry(void* out, const void* q, const void* k, const void* 
                            const int32_t* cu_seqlens, int batch, int max_seqlen, int num_heads,
                            int num_kv_heads, int head_size, int64_t q_stride, int64_t k_stride,
                            int64_t v_stride, float scale, int causal, const float* alibi_slopes, int window,
-                           int dtype, void* stream) {
+                           int dtype, void* stream, float softcap = 0.f) {
   APHRO_CHECK(window <= 0 || causal, "flash_attn_varlen: a sliding window needs causal attention");
   APHRO_CHECK(dtype == APHRO_F16 || dtype == APHRO_BF16, "flash_attn_varlen: dtype must be f16 or bf16");
+  APHRO_CHECK(softcap >= 0.f && (softcap == 0.f || head_size == 128 || head_size == 256),
+              "flash_attn_varlen: a logit soft cap (>= 0) is served for head_size 128 / 256 only; got softcap=%g head_size=%d",
+              (double)softcap, head_size);
   APHRO_CHECK(num_kv_heads > 0 && num_heads % num_kv_heads == 0, "flash_attn_varlen: bad head counts");
   APHRO_CHECK(q_stride % 8 == 0 && k_stride % 8 == 0 && v_stride % 8 == 0, "flash_attn_varlen: strides must be multiples of 8");
   APHRO_CHECK(((uintptr_t)q % 16) == 0 && ((uintptr_t)k % 16) == 0 && ((uintptr_t)v % 16) == 0, "flash_attn_varlen: 16-byte alignment");
   if (batch == 0 || max_seqlen == 0) return APHRO_OK;
   FAParams p;
+  p.softcap = softcap;
   p.out = out; p.q = q; p.k = k; p.v = v; p.cu_seqlens = cu_seqlens; p.alibi = alibi_slopes;
   p.num_heads = num_heads; p.num_kv_heads = num_kv_heads;
   p.q_stride = q_stride; p.k_stride = k_stride; p.v_stride = v_stride;
@@ -1261,3 +1340,13 @@ extern "C" int aphro_flash_attn_varlen_window(void* out, const void* q, const vo
                          v_stride, scale, causal, alibi_slopes, window, dtype, stream);
 }
 
+// Sliding window (<= 0: none) and logit soft cap (0: none) in one signature: logit = softcap * tanh(scale * q.k / softcap),
+// then the ALiBi bias, then the causal / window / length mask (flash-attention's softcap= order).  Head sizes 128 / 256.
+extern "C" int aphro_flash_attn_varlen_softcap(void* out, const void* q, const void* k, const void* v,
+                                               const int32_t* cu_seqlens, int batch, int max_seqlen, int num_heads,
+                                               int num_kv_heads, int head_size, int64_t q_stride, int64_t k_stride,
+                                               int64_t v_stride, float scale, int causal, const float* alibi_slopes,
+                                               int window, float softcap, int dtype, void* stream) {
+  return fa_varlen_entry(out, q, k, v, cu_seqlens, batch, max_seqlen, num_heads, num_kv_heads, head_size, q_stride, k_stride,
+                         v_stride, scale, causal, alibi_slopes, window, dtype, stream, softcap);
+}

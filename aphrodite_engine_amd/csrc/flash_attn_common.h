@@ -19,6 +19,7 @@ struct FAParams {
   const int32_t* cu_seqlens_k;   // third-generation kernel: key rows per sequence when they differ from the query rows
   int64_t o_stride;              // ... and the output row stride (elements)
   int window;                    // first / second generation kernels: sliding window (keys > query position - window), 0 = off
+  float softcap;                 // first / second generation kernels, CAP instantiations: logit soft cap, 0 = off
 };
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));

@@ -55,7 +55,11 @@ __device__ __forceinline__ void fa4_qk_mfma(f32x16& acc, u32x4 kfrag, u32x4 qfra
   }
 }
 
-template <typename T>
+// CAP: logit soft cap (Gemma-2), a separate instantiation: logit = cap * tanh(scale * q.k / cap) in the log2 domain through
+// softcap_logit (common.h).  tanh is monotonic, so on unmasked tiles the row maximum is still taken on the raw scores and only
+// the maximum itself is capped; each exponential then takes the capped score: v_mul, v_exp, v_add, v_rcp, v_fma in front of
+// the v_sub + v_exp that replace the uncapped v_fma + v_exp -- all inside the softmax slices that sit between MFMAs.
+template <typename T, bool CAP = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void flash_attn_varlen_v4_kernel(FAParams p) {
   constexpr int HD = 128, BM = 256, BN = 64;
@@ -102,7 +106,9 @@ void flash_attn_varlen_v4_kernel(FAParams p) {
     for (int ks = 0; ks < 8; ++ks) qf[qb][ks] = *reinterpret_cast<const u32x4*>(qp + 16 * ks);
   }
   const float slope2 = (p.alibi ? p.alibi[head] : 0.f) * 1.44269504088896f;
-  const float c2 = p.scale * 1.44269504088896f;
+  // capped form: c2 = the argument scale of softcap_logit, cap2 = the cap in the log2 domain
+  const float c2 = CAP ? p.scale * (2.f * 1.44269504088896f) / p.softcap : p.scale * 1.44269504088896f;
+  const float cap2 = p.softcap * 1.44269504088896f;
 
   // ---- K / V staging: 16 pieces of 4 keys (1 KiB) per tile; wave w issues pieces 4 w .. 4 w + 3 of K and of V -------------
   const uint16_t* kbase = (const uint16_t*)p.k + (size_t)k_row0 * p.k_stride + (size_t)kvh * HD;
@@ -191,7 +197,9 @@ void flash_attn_varlen_v4_kernel(FAParams p) {
 #pragma unroll
         for (int r = r0; r < r0 + 4; ++r) {
           const int key = it * BN + 32 * b + 8 * (r >> 2) + 4 * kh + (r & 3);
-          const float x = s[b][r] * c2 + slope2 * (float)(key - qpos);
+          float x;
+          if constexpr (CAP) x = softcap_logit(s[b][r], c2, cap2) + slope2 * (float)(key - qpos);
+          else x = s[b][r] * c2 + slope2 * (float)(key - qpos);
           s[b][r] = key <= lim ? x : -1e30f;          // in place: the scores are VGPRs
         }
       }
@@ -201,7 +209,9 @@ void flash_attn_varlen_v4_kernel(FAParams p) {
       st.mx = mx;
     } else if (sl == 4) {
       if (h == 0) {
-        float mx = MASK ? st.mx : st.mx * c2;          // scale > 0: the maximum commutes with it
+        float mx;                                      // scale > 0 (and tanh monotonic): the maximum commutes with it
+        if constexpr (CAP) mx = MASK ? st.mx : softcap_logit(st.mx, c2, cap2);
+        else mx = MASK ? st.mx : st.mx * c2;
         st.mx = __builtin_fmaxf(mx, other_half(mx));
       } else {
         st.alpha = new_max(qb, st.mx);
@@ -218,7 +228,8 @@ void flash_attn_varlen_v4_kernel(FAParams p) {
           const float ex = __builtin_amdgcn_exp2f(s[b][r0 + i] - st.m_new);
           x[i] = s[b][r0 + i] > -1e29f ? ex : 0.f;
         } else {
-          x[i] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[b][r0 + i], c2, -st.m_new));
+          if constexpr (CAP) x[i] = __builtin_amdgcn_exp2f(softcap_logit(s[b][r0 + i], c2, cap2) - st.m_new);
+          else x[i] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[b][r0 + i], c2, -st.m_new));
         }
         st.lsum += x[i];
       }
@@ -423,13 +434,18 @@ int fa_v4_launch(const FAParams& p, int dtype, int batch, hipStream_t st) {
   bool& attr_set = attr_set_dev[device_slot()];
   if (!attr_set) {
     if (hipFuncSetAttribute((const void*)flash_attn_varlen_v4_kernel<Half>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess ||
-        hipFuncSetAttribute((const void*)flash_attn_varlen_v4_kernel<BFloat>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) {
+        hipFuncSetAttribute((const void*)flash_attn_varlen_v4_kernel<BFloat>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess ||
+        hipFuncSetAttribute((const void*)flash_attn_varlen_v4_kernel<Half, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess ||
+        hipFuncSetAttribute((const void*)flash_attn_varlen_v4_kernel<BFloat, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) {
       set_error("flash attention: cannot raise the dynamic LDS limit");
       return APHRO_ERR_LAUNCH;
     }
     attr_set = true;
   }
-  if (dtype == APHRO_F16) hipLaunchKernelGGL((flash_attn_varlen_v4_kernel<Half>), grid, dim3(256), LDS, st, p);
+  if (p.softcap > 0.f) {
+    if (dtype == APHRO_F16) hipLaunchKernelGGL((flash_attn_varlen_v4_kernel<Half, true>), grid, dim3(256), LDS, st, p);
+    else hipLaunchKernelGGL((flash_attn_varlen_v4_kernel<BFloat, true>), grid, dim3(256), LDS, st, p);
+  } else if (dtype == APHRO_F16) hipLaunchKernelGGL((flash_attn_varlen_v4_kernel<Half>), grid, dim3(256), LDS, st, p);
   else hipLaunchKernelGGL((flash_attn_varlen_v4_kernel<BFloat>), grid, dim3(256), LDS, st, p);
   APHRO_LAUNCH_CHECK();
   return APHRO_OK;

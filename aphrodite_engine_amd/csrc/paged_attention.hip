@@ -58,6 +58,9 @@ struct PAParams {
   void* out_pairs;     // ... and `out` in the pair-major layout that GEMM reads lane-linearly (common.h aq_pair_offset; out may be NULL)
   float scale;         // softmax scale * k_scale
   float v_scale;
+  // logit soft cap (CAP instantiations only; 0: off): logit = softcap * tanh(q.k * softmax scale * k_scale / softcap).
+  // `scale` then holds softmax scale * k_scale * 2 log2(e) / softcap, the argument scale of softcap_logit (common.h)
+  float softcap;
   int64_t q_stride, kv_block_stride, kv_head_stride;
   // ---- fused QKV-slab reduce + rotary embedding + cache write (decode fast path) ----
   // When qkv_slabs != NULL the kernel takes q/k/v of the NEW token of every sequence from the
@@ -148,7 +151,9 @@ __device__ __forceinline__ u32x2 fp8x4_to_T(uint32_t w) {
 // Kernel arguments: the head of the dependent chain (sequence length -> block table -> K/V addresses) and the sizes every
 // address needs come first and as scalars, so that they are preloaded into SGPRs (Makefile: -amdgpu-kernarg-preload-count);
 // p_in carries the rest, its copies of the leading fields are not read.
-template <typename T, int KV, int HD, int BS, int NW, int ROPE, bool SPLIT = false>
+// CAP: the logit soft cap (Gemma-2), plain form (ROPE == 0; unsplit and split) only.  A separate instantiation for the same
+// reason as ROPE: the uncapped kernels keep their code and their register budget bit for bit.
+template <typename T, int KV, int HD, int BS, int NW, int ROPE, bool SPLIT = false, bool CAP = false>
 __global__ __launch_bounds__(NW * 64) void paged_attention_kernel(const int32_t* seq_lens, const int32_t* block_tables,
                                                                   const void* kc_, const void* vc_, const float* qkv_slabs,
                                                                   int num_heads, int num_kv_heads, int max_blocks_per_seq,
@@ -173,6 +178,7 @@ __global__ __launch_bounds__(NW * 64) void paged_attention_kernel(const int32_t*
   // instead of 16; configs[2] attention 94.6 -> 90.6 us).  With 16-bit KV the same map measured +2.4 us per launch at ctx
   // 1024 and +-0 at 8192 (profiles/r6_decode_experiments.txt (5)): not used there.
   constexpr bool TOK8 = FP8;
+  static_assert(!CAP || ROPE == 0, "the soft-cap form is the plain kernel (unsplit or split) only");
   using VRaw = u32x2;                           // TOK8: a lane's 8 fp8 tokens of one V row; else 4 tokens (fp8: in [0])
   constexpr int NVJ = TOK8 ? 1 : 2;             // V loads per d-tile
   auto tok_of_k_row = [](int jj, int c) { return TOK8 ? 8 * (c >> 2) + 4 * jj + (c & 3) : 16 * jj + c; };
@@ -424,7 +430,11 @@ __global__ __launch_bounds__(NW * 64) void paged_attention_kernel(const int32_t*
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           int tok = tb + tok_of_s_row(jj, g, r);
-          float x = s[jj][r] * p.scale + slope * (float)(tok - seq_len + 1);
+          float x;
+          // capped: scale, cap, THEN the ALiBi bias (flash-attention's order); two transcendentals per score, issued
+          // between the QK and the PV MFMAs of the pair while the other waves' K/V loads are in flight
+          if constexpr (CAP) x = softcap_logit(s[jj][r], p.scale, p.softcap) + slope * (float)(tok - seq_len + 1);
+          else x = s[jj][r] * p.scale + slope * (float)(tok - seq_len + 1);
           bool ok = tok >= pstart && tok < pend;
           x = ok ? x : -1e30f;
           pv[jj][r] = x;
@@ -944,17 +954,23 @@ __global__ void convert_fp8_kernel(void* __restrict__ dst, const void* __restric
 }
 
 // ---------------------------------------------------------------------------
-template <typename T, int KV, int HD, int BS, int ROPE = 0>
+template <typename T, int KV, int HD, int BS, int ROPE = 0, bool CAP = false>
 static int launch_pa(const PAParams& p, int num_seqs, int parts, int nw, hipStream_t st) {
   dim3 grid((unsigned)p.num_kv_heads, (unsigned)num_seqs, (unsigned)parts);
   size_t lds = ((size_t)nw * 16 * 2 + (size_t)nw * p.nh_lds * HD) * sizeof(float);
 #define APHRO_PA_LAUNCH(NWV, SPL)                                                                   \
   {                                                                                                 \
-    auto kern = paged_attention_kernel<T, KV, HD, BS, NWV, ROPE, SPL>;                              \
+    auto kern = paged_attention_kernel<T, KV, HD, BS, NWV, ROPE, SPL, CAP>;                             \
     if (lds > 64 * 1024)                                                                            \
       (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
     hipLaunchKernelGGL(kern, grid, dim3(NWV * 64), lds, st, p.seq_lens, p.block_tables, p.kc, p.vc, p.qkv_slabs,        \
                        p.num_heads, p.num_kv_heads, p.max_blocks_per_seq, p.partition_size, p);                  \
+  }
+  // capped head 256 with a 16-bit cache: four waves only -- the eight-wave form does not fit 256 registers (the uncapped one
+  // spills 116 bytes per lane to scratch there); one wave per SIMD may use the accumulator file as well and needs none
+  if constexpr (CAP && HD == 256 && KV == 0) {
+    nw = 4;
+    lds = ((size_t)nw * 16 * 2 + (size_t)nw * p.nh_lds * HD) * sizeof(float);
   }
   if constexpr (HD == 128 && (BS == 16 || BS == 32)) {   // the split form is instantiated for the serving geometry only
     if (p.nsplit > 1) {
@@ -964,7 +980,8 @@ static int launch_pa(const PAParams& p, int num_seqs, int parts, int nw, hipStre
       return APHRO_OK;
     }
   }
-  if (nw == 4) APHRO_PA_LAUNCH(4, false)
+  if constexpr (CAP && HD == 256 && KV == 0) APHRO_PA_LAUNCH(4, false)
+  else if (nw == 4) APHRO_PA_LAUNCH(4, false)
   else APHRO_PA_LAUNCH(8, false)
 #undef APHRO_PA_LAUNCH
   APHRO_LAUNCH_CHECK();
@@ -983,6 +1000,17 @@ static int dispatch_pa(const PAParams& p, int num_seqs, int parts, int nw, int h
       if (block_size == 32) return launch_pa<T, KV, 128, 32, 1>(p, num_seqs, parts, nw, st);
     }
     set_error("paged_attention: the fused rotary form supports block_size 16 / 32");
+    return APHRO_ERR_INVALID;
+  }
+  if (p.softcap > 0.f) {   // the soft-cap form: the head sizes of the models that use one (checked by the caller)
+#define APHRO_PA_CAP_CASE(HDV, BSV) \
+  if (head_size == HDV && block_size == BSV) return launch_pa<T, KV, HDV, BSV, 0, true>(p, num_seqs, parts, nw, st);
+    APHRO_PA_CAP_CASE(128, 8)
+    APHRO_PA_CAP_CASE(128, 16)
+    APHRO_PA_CAP_CASE(128, 32)
+    APHRO_PA_CAP_CASE(256, 16)
+#undef APHRO_PA_CAP_CASE
+    set_error("paged_attention: no soft-cap kernel for head_size=%d / block_size=%d", head_size, block_size);
     return APHRO_ERR_INVALID;
   }
 #define APHRO_PA_CASE(HDV, BSV) \
@@ -1060,7 +1088,7 @@ static int paged_attention_impl(void* out, void* out_packed, float* exp_sums, fl
                                      const int64_t* slot_mapping = nullptr, const float* slab_row_scale = nullptr,
                                      const float* slab_col_scale = nullptr, void* out_q8 = nullptr,
                                      const float* out_q8_scale = nullptr, float* out_absmax = nullptr,
-                                     void* out_pairs = nullptr) {
+                                     void* out_pairs = nullptr, float softcap = 0.f) {
   hipStream_t st = (hipStream_t)stream;
   APHRO_CHECK(dtype == APHRO_F16 || dtype == APHRO_BF16, "paged_attention: query dtype must be f16 or bf16");
   APHRO_CHECK(kv_dtype >= APHRO_KV_AUTO && kv_dtype <= APHRO_KV_FP8_E5M2, "Unsupported data type of kv cache: %d", kv_dtype);
@@ -1068,6 +1096,12 @@ static int paged_attention_impl(void* out, void* out_packed, float* exp_sums, fl
   APHRO_CHECK(partition_size >= 0 && partition_size % 32 == 0, "paged_attention: partition size must be a multiple of 32");
   APHRO_CHECK(qkv_slabs != nullptr || (q_stride % 8 == 0 && ((uintptr_t)query % 16) == 0),
               "paged_attention: query must be 16-byte aligned");
+  APHRO_CHECK(softcap >= 0.f, "paged_attention: softcap must be >= 0 (0 = off)");
+  APHRO_CHECK(softcap == 0.f || (qkv_slabs == nullptr && out_packed == nullptr &&
+                                 ((head_size == 128 && (block_size == 8 || block_size == 16 || block_size == 32)) ||
+                                  (head_size == 256 && block_size == 16))),
+              "paged_attention: a logit soft cap is served by the plain form for head_size 128 (block_size 8 / 16 / 32) and "
+              "256 (block_size 16) only; got head_size=%d block_size=%d", head_size, block_size);
   if (num_seqs == 0) return APHRO_OK;
   PAParams p;
   p.qkv_slabs = qkv_slabs; p.nslab = nslab; p.positions = positions; p.cos_sin = (const uint16_t*)cos_sin;
@@ -1099,6 +1133,8 @@ static int paged_attention_impl(void* out, void* out_packed, float* exp_sums, fl
   p.num_heads = num_heads; p.num_kv_heads = num_kv_heads;
   p.max_blocks_per_seq = max_num_blocks_per_seq;
   p.scale = scale * (kv_dtype == APHRO_KV_AUTO ? 1.f : k_scale);
+  p.softcap = softcap;
+  if (softcap > 0.f) p.scale *= 2.f * 1.44269504088896f / softcap;
   p.v_scale = kv_dtype == APHRO_KV_AUTO ? 1.f : v_scale;
   p.q_stride = q_stride; p.kv_block_stride = kv_block_stride; p.kv_head_stride = kv_head_stride;
   const int gqa = num_heads / num_kv_heads;
@@ -1182,6 +1218,24 @@ extern "C" int aphro_paged_attention(void* out, float* exp_sums, float* max_logi
                               max_num_blocks_per_seq, block_size, max_seq_len, alibi_slopes, q_stride,
                               kv_block_stride, kv_head_stride, dtype, kv_dtype, k_scale, v_scale, partition_size,
                               stream);
+}
+
+// The same op with a logit soft cap (Gemma-2): logit = softcap * tanh(scale * k_scale * q.k / softcap) + ALiBi bias.
+// softcap == 0: exactly aphro_paged_attention.
+extern "C" int aphro_paged_attention_softcap(void* out, float* exp_sums, float* max_logits, void* tmp_out,
+                                             const void* query, const void* key_cache, const void* value_cache,
+                                             int num_seqs, int num_heads, int num_kv_heads, int head_size,
+                                             float scale, const int32_t* block_tables, const int32_t* seq_lens,
+                                             int max_num_blocks_per_seq, int block_size, int max_seq_len,
+                                             const float* alibi_slopes, int64_t q_stride, int64_t kv_block_stride,
+                                             int64_t kv_head_stride, int dtype, int kv_dtype, float k_scale,
+                                             float v_scale, int partition_size, float softcap, void* stream) {
+  return paged_attention_impl(out, nullptr, exp_sums, max_logits, tmp_out, query, key_cache, value_cache, num_seqs,
+                              num_heads, num_kv_heads, head_size, scale, block_tables, seq_lens,
+                              max_num_blocks_per_seq, block_size, max_seq_len, alibi_slopes, q_stride,
+                              kv_block_stride, kv_head_stride, dtype, kv_dtype, k_scale, v_scale, partition_size,
+                              stream, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                              nullptr, softcap);
 }
 
 // v1-form decode attention whose output is (also) written fragment-major for the

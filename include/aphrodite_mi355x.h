@@ -227,6 +227,25 @@ int aphro_paged_attention(void* out, float* exp_sums, float* max_logits,
                           float k_scale, float v_scale, int partition_size,
                           void* stream);
 
+/* The same op with an attention logit soft cap (Gemma-2; flash-attention's softcap=):
+ *   logit = softcap * tanh(scale * k_scale * (q . k) / softcap) + alibi bias,
+ * then the sequence-length mask and the softmax.  In the partitioned form
+ * max_logits / exp_sums hold the capped logits.  Served by a compile-time variant
+ * of the decode kernel for head_size 128 (block_size 8 / 16 / 32) and 256
+ * (block_size 16), f16 / bf16, every KV type, any GQA ratio; other geometries are
+ * refused.  softcap == 0: aphro_paged_attention. */
+int aphro_paged_attention_softcap(void* out, float* exp_sums, float* max_logits,
+                                  void* tmp_out, const void* query, const void* key_cache,
+                                  const void* value_cache, int num_seqs, int num_heads,
+                                  int num_kv_heads, int head_size, float scale,
+                                  const int32_t* block_tables, const int32_t* seq_lens,
+                                  int max_num_blocks_per_seq, int block_size,
+                                  int max_seq_len, const float* alibi_slopes,
+                                  int64_t q_stride, int64_t kv_block_stride,
+                                  int64_t kv_head_stride, int dtype, int kv_dtype,
+                                  float k_scale, float v_scale, int partition_size,
+                                  float softcap, void* stream);
+
 /* Same kernel in its single-launch (v1) form, additionally writing the output
  * fragment-major (f16) for the o_proj GEMM of the decode fast path; `out` may be
  * NULL. */
@@ -403,6 +422,15 @@ int aphro_flash_attn_varlen_window(void* out, const void* q, const void* k, cons
                                    int64_t q_stride, int64_t k_stride, int64_t v_stride,
                                    float scale, int causal, const float* alibi_slopes,
                                    int window, int dtype, void* stream);
+/* Window (<= 0: none) and logit soft cap (0: none) in one signature: logit = softcap * tanh(scale * (q . k) / softcap),
+ * then the ALiBi bias, then the causal / window / length mask.  Head sizes 128 / 256 when softcap > 0 (the first / second
+ * generation tile machines' capped instantiations). */
+int aphro_flash_attn_varlen_softcap(void* out, const void* q, const void* k, const void* v,
+                                    const int32_t* cu_seqlens, int batch, int max_seqlen,
+                                    int num_heads, int num_kv_heads, int head_size,
+                                    int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                                    float scale, int causal, const float* alibi_slopes,
+                                    int window, float softcap, int dtype, void* stream);
 
 /* Prefill with cached context -- the context_attention_fwd role
  *   attention/ops/prefix_prefill.py:696-858 (kernel :58-255), called through
@@ -440,6 +468,16 @@ int aphro_context_attention_gathered(void* out, const void* q, const void* k, co
                                      int64_t k_stride, int64_t v_stride, int64_t o_stride, float scale, float k_scale,
                                      float v_scale, const float* alibi_slopes, int sliding_window, int dtype,
                                      int kv_dtype, void* workspace, size_t workspace_bytes, void* stream);
+/* ... with a logit soft cap after sliding_window (0: none; head_size 128 / 256): softcap * tanh(scale * (q . k) / softcap) over
+ * the gathered (dequantised) keys.  `scale` is the layer's softmax scale -- Gemma-2 27B's is not 1/sqrt(hd). */
+int aphro_context_attention_gathered_softcap(void* out, const void* q, const void* k, const void* v, const void* k_cache,
+                                             const void* v_cache, const int32_t* block_tables, const int32_t* q_start_loc,
+                                             const int32_t* seq_lens, const int32_t* ctx_lens, int batch, int max_query_len,
+                                             int max_seq_len, int64_t total_kv_tokens, int max_blocks, int num_heads,
+                                             int num_kv_heads, int head_size, int block_size, int x, int64_t q_stride,
+                                             int64_t k_stride, int64_t v_stride, int64_t o_stride, float scale, float k_scale,
+                                             float v_scale, const float* alibi_slopes, int sliding_window, float softcap,
+                                             int dtype, int kv_dtype, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
  * FP8 (W8A8, per-token dynamic activation scale) decode fast path -- configs[2],
