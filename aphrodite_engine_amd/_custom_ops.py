@@ -565,6 +565,64 @@ def _wna16_large(a, qweight, qzeros, scales, perm, zero_offset):
     return out
 
 
+# Rows at which GROUP-SIZE-32 int4 weights (exllama order) go to their own prompt-sized kernel (csrc/wna16_gemm_large_g32.hip;
+# wna16_gemm_large.hip tiles group sizes that are multiples of 64 only) instead of 64-row passes of the decode kernel (below
+# GPTQ_DEQUANT_MIN_M rows) or gptq_dequant + a library GEMM (from there).  MIN_M .. MAX_M is the contiguous range of measured
+# row counts at which the kernel wins on EVERY measured shape in both runs (the rule of GPTQ_GIDX_LARGE_MAX_M):
+# tools/wna16_g32_bench.py, profiles/wna16_gemm_large_g32.txt, DESIGN.md "wna16_gemm_large_g32".  Old / new time, both runs,
+# Llama-3-8B qkv / o / gate_up / down and 70B-at-TP-8 o / down, act-order, f16 (runs agree within 3 %):
+#   M =   65: 1.03-1.07 / 0.93-0.94 / 1.94 / 1.46 / 0.78 / 1.01   (o_proj loses: 2 launches + slabs against 2 decode passes)
+#   M =   96: 1.21 / 0.89-0.91 / 2.07 / 1.48 / 0.88 / 1.07        M = 128: 1.18 / 1.01-1.04 / 2.67 / 1.73 / 0.82 / 1.10
+#   M =  192: 1.24 / 1.38 / 2.64 / 1.73 / 1.05 / 1.37             M = 256: 1.95 / 1.57 / 2.57 / 2.15 / 1.45 / 1.98
+#   M =  512: 1.42 / 1.42 / 2.06 / 1.66 / 1.08 / 1.35             M = 1024: 1.11 / 1.14 / 1.47 / 1.20 / 1.35 / 1.24
+#   M = 2048: 0.82-0.84 (qkv: one and a half rounds of workgroups) / 1.06 / 1.14 / 1.06 / 1.28 / 1.12
+#   M = 4096: 0.92 / 1.00 / 0.99-1.01 / 1.00 / 1.10 / 0.99        M = 8192: 0.94 / 0.94 / 0.91-0.93 / 0.94 / 0.98-1.00 / 0.94
+# So the kernel does NOT win at the largest row counts (library GEMM at ~1.2 PFLOP/s, reconstruction amortised) nor on the
+# small o_proj shapes below 192 rows; outside 192 .. 1024 the old paths and their log line stay.  129 .. 191 and
+# 1025 .. 2047 rows were not measured.  csrc_torch/torch_bindings.cpp carries the same numbers.
+WNA16_G32_LARGE_MIN_M = 192
+WNA16_G32_LARGE_MAX_M = 1024
+
+
+def wna16_large_g32_ok(m: int, n: int, k: int, groups: int, dtype: torch.dtype) -> bool:
+    return dtype in _DT and bool(_lib.lib().aphro_wna16_gemm_large_g32_supported(m, n, k, groups, _dt_of(dtype)))
+
+
+def _wna16_g32_routed(m: int, n: int, k: int, groups: int, a_dtype: torch.dtype, s_dtype: torch.dtype) -> bool:
+    """The one routing rule of the group-32 kernel (ops._wna16, gptq_gemm, wna16_linear_strip)."""
+    return WNA16_G32_LARGE_MIN_M <= m <= WNA16_G32_LARGE_MAX_M and a_dtype == s_dtype \
+        and wna16_large_g32_ok(m, n, k, groups, a_dtype) and not switch("APHRO_WNA16_NO_LARGE")
+
+
+def wna16_gemm_large_g32(a: torch.Tensor, qweight: torch.Tensor, qzeros: torch.Tensor, scales: torch.Tensor,
+                         zero_offset: int) -> torch.Tensor:
+    """a [M, K] x int4 weights of GROUP SIZE 32 (qweight int32 [K/8, N] in exllama order after gptq_shuffle, qzeros int32
+    [K/32, N/8], scales [K/32, N]; zero_offset 1 = GPTQ, 0 = AWQ-repacked / compressed-tensors) for prompt-sized M:
+    csrc/wna16_gemm_large_g32.hip.  Act-order: pass a[:, perm]."""
+    _require_cuda(a, qweight, qzeros, scales)
+    m, k = a.shape
+    n, groups = qweight.shape[1], scales.shape[0]
+    if a.dtype != scales.dtype:
+        raise RuntimeError("wna16_gemm_large_g32: activations and scales must share a dtype")
+    if qweight.shape[0] * 8 != k or tuple(qzeros.shape) != (groups, n // 8) or scales.shape[1] != n:
+        raise RuntimeError("wna16_gemm_large_g32: shape mismatch")
+    out = torch.empty((m, n), dtype=a.dtype, device=a.device)
+    if m == 0:
+        return out
+    if not wna16_large_g32_ok(m, n, k, groups, a.dtype):
+        raise RuntimeError(f"wna16_gemm_large_g32: M={m} N={n} K={k} groups={groups} {a.dtype} is not served by the kernel")
+    if a.stride(1) != 1 or a.stride(0) % 8 != 0 or a.data_ptr() % 16 != 0:
+        a = a.contiguous()
+    qweight, qzeros, scales = qweight.contiguous(), qzeros.contiguous(), scales.contiguous()
+    lib = _lib.lib()
+    nbytes = lib.aphro_wna16_gemm_large_g32_workspace_bytes(m, n, k, groups, _dt(a))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=a.device)        # (the caching allocator: capturable)
+    check(lib.aphro_wna16_gemm_large_g32(a.data_ptr(), a.stride(0), qweight.data_ptr(), qzeros.data_ptr(), scales.data_ptr(),
+                                         out.data_ptr(), ws.data_ptr(), nbytes, m, n, k, groups, zero_offset, _dt(a),
+                                         _stream()), "wna16_gemm_large_g32")
+    return out
+
+
 def wna16_gemm_large_silu_supported(m: int, n: int, k: int, groups: int) -> bool:
     return bool(_lib.lib().aphro_wna16_gemm_large_silu_supported(m, n, k, groups)) and m * k * 2 < 2 ** 32
 
@@ -660,6 +718,8 @@ def wna16_linear_strip(a: torch.Tensor, strip: torch.Tensor, qzeros: torch.Tenso
     if large:
         return wna16_gemm_large_strip(a, strip, qzeros, scales, zero_offset, strip_m=strip_m)
     qweight = wna16_strip_unrelayout(strip, strip_m, groups)
+    if _wna16_g32_routed(m, n, k, groups, a.dtype, scales.dtype):      # group size 32: its own prompt-sized kernel
+        return wna16_gemm_large_g32(a, qweight, qzeros, scales, zero_offset)
     if m >= GPTQ_DEQUANT_MIN_M:         # gptq_gemm's own rule where the tile machine does not take the call
         _library_fallback("wna16_linear_strip", f"M={m} N={n} K={k}: " + ("APHRO_WNA16_NO_LARGE is set" if switch("APHRO_WNA16_NO_LARGE")
                           else "shape not tiled by wna16_gemm_large") + " (strip_unrelayout + gptq_dequant + matmul)")
@@ -703,6 +763,8 @@ def _wna16(a, qweight, qzeros, scales, perm, zero_offset):
     if wna16_large_ok(m, n, k, scales.shape[0]) and wna16_prefers_large(m, n, k) \
             and not switch("APHRO_WNA16_NO_LARGE"):
         return _wna16_large(a, qweight, qzeros, scales, perm, zero_offset)
+    if _wna16_g32_routed(m, n, k, scales.shape[0], a.dtype, scales.dtype):
+        return wna16_gemm_large_g32(a[:, perm.long()] if perm is not None else a, qweight, qzeros, scales, zero_offset)
     if wna16_prefers_mid(m, n, k) and wna16_mid_ok(m, n, k, scales.shape[0]) and not switch("APHRO_WNA16_NO_MID"):
         return _wna16_mid(a, qweight, qzeros, scales, perm, zero_offset)
     lib = _lib.lib()
@@ -834,6 +896,8 @@ def gptq_gemm(a: torch.Tensor, b_q_weight: torch.Tensor,
         return gptq_gemm_gidx_large(a, b_q_weight, b_gptq_qzeros, b_gptq_scales, b_g_idx, 1)
     large = use_exllama and wna16_large_ok(m, b_q_weight.shape[1], a.shape[1], b_gptq_scales.shape[0]) \
         and wna16_prefers_large(m, b_q_weight.shape[1], a.shape[1]) and not switch("APHRO_WNA16_NO_LARGE")
+    large = large or (use_exllama and _wna16_g32_routed(m, b_q_weight.shape[1], a.shape[1], b_gptq_scales.shape[0], a.dtype,
+                                                       b_gptq_scales.dtype))       # group size 32: _wna16 routes it
     if not use_exllama or (m >= GPTQ_DEQUANT_MIN_M and not large):
         w = gptq_dequant(b_q_weight, b_gptq_qzeros, b_gptq_scales, b_g_idx,
                          use_exllama, bit)

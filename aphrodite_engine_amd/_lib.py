@@ -132,6 +132,9 @@ SIGNATURES = {
     "aphro_gptq8_gemm_large_supported": (I, [L, L, L, L, I]),
     "aphro_gptq8_gemm_large_workspace_bytes": (Z, [L, L, L, L, I]),
     "aphro_gptq8_gemm_large": (I, [P, L, P, P, P, P, P, Z, L, L, L, L, I, P]),
+    "aphro_wna16_gemm_large_g32_supported": (I, [L, L, L, L, I]),
+    "aphro_wna16_gemm_large_g32_workspace_bytes": (Z, [L, L, L, L, I]),
+    "aphro_wna16_gemm_large_g32": (I, [P, L, P, P, P, P, P, Z, L, L, L, L, I, I, P]),
     "aphro_gptq_gemm_gidx_supported": (I, [L, L, L, L, I]),
     "aphro_gptq_gemm_gidx_workspace_bytes": (Z, [L, L, L]),
     "aphro_gptq_gemm_gidx": (I, [P, L, P, P, P, P, P, P, Z, L, L, L, L, I, I, P]),

@@ -137,6 +137,21 @@ torch::Tensor gptq_gemm(torch::Tensor a, torch::Tensor b_q_weight, torch::Tensor
        "gptq_gemm");
     return out;
   }
+  // group size 32 at prompt sizes: csrc/wna16_gemm_large_g32.hip at WNA16_G32_LARGE_MIN_M .. WNA16_G32_LARGE_MAX_M rows (the
+  // Python op's constants of the same names: the two must agree; measured, profiles/wna16_gemm_large_g32.txt)
+  constexpr int64_t WNA16_G32_LARGE_MIN_M = 192, WNA16_G32_LARGE_MAX_M = 1024;
+  if (m >= WNA16_G32_LARGE_MIN_M && m <= WNA16_G32_LARGE_MAX_M && getenv("APHRO_WNA16_NO_LARGE") == nullptr &&
+      a.scalar_type() == b_gptq_scales.scalar_type() && aphro_wna16_gemm_large_g32_supported(m, n, k, groups, act_dtype(a))) {
+    torch::Tensor ag = act_order ? a.index_select(1, b_g_idx.to(torch::kLong)) : a;
+    if (ag.stride(0) % 8 != 0 || ((uintptr_t)ag.data_ptr() % 16) != 0) ag = ag.clone(at::MemoryFormat::Contiguous);
+    auto ws32 = torch::empty({(int64_t)aphro_wna16_gemm_large_g32_workspace_bytes(m, n, k, groups, act_dtype(a))},
+                             a.options().dtype(torch::kUInt8));
+    ok(aphro_wna16_gemm_large_g32(ag.data_ptr(), ag.stride(0), (const uint32_t*)b_q_weight.data_ptr(),
+                                  (const uint32_t*)b_gptq_qzeros.data_ptr(), b_gptq_scales.data_ptr(), out.data_ptr(),
+                                  ws32.data_ptr(), (size_t)ws32.numel(), m, n, k, groups, 1, act_dtype(a), cur_stream()),
+       "gptq_gemm");
+    return out;
+  }
   auto ws = torch::empty({(int64_t)aphro_wna16_workspace_bytes(m < 64 ? m : 64, n, k)}, a.options().dtype(torch::kUInt8));
   torch::Tensor tmp;
   if (act_order) tmp = torch::empty({m < 64 ? m : 64, k}, a.options());

@@ -928,6 +928,29 @@ int aphro_gptq8_gemm_large(const void* a, int64_t lda, const uint32_t* q_weight,
                            void* c, void* workspace, size_t workspace_bytes, int64_t M, int64_t N, int64_t K,
                            int64_t groups, int dtype, void* stream);
 
+/* W4A16 at PROMPT sizes (M > 64) for GROUP SIZE 32 (`gptq-4bit-32g` checkpoints, compressed-tensors W4A16 group 32): the
+ * role of reconstruct + hipBLAS in `_C::gptq_gemm` (q_gemm.cu:1529-1544) and of `_C::gptq_marlin_gemm`
+ * (kernels/torch_bindings.cpp:195-201) for the group size aphro_wna16_gemm_large does not tile.
+ * csrc/wna16_gemm_large_g32.hip.
+ *   c[M, N] = a[M, K] . W,  W[k][n] = (q[k][n] - (qzero[k / 32][n] + zero_offset)) * scale[k / 32][n]
+ * a: [M, lda] f16 | bf16 (lda in elements, lda % 8 == 0, lda >= K, 16-byte aligned); act-order: pass a[:, perm].
+ * q_weight: int32 [K/8, N] in the exllama-shuffled order (aphro_gptq_shuffle); qzeros int32 [groups, N/8]; scales
+ * [groups, N] in a's dtype; zero_offset 1 (GPTQ) | 0 (AWQ-repacked, compressed-tensors); c [M, N] in a's dtype, 16-byte
+ * aligned.  Arithmetic of aphro_wna16_gemm_large: (q - z) exact, one f16 rounding in the multiply by the group scale, fp32
+ * accumulation, one rounding of the sum; bf16: activations widened to f16 with saturation (into the workspace), scales
+ * converted to f16, output rounded to bf16 (RNE).  Scales and zeros stream through LDS with the weights (nothing grows
+ * with K).  Small grids cut K into slices whose fp32 slabs (workspace) are added in slice order by a second launch:
+ * deterministic, bit-equal run to run, no flags or atomics -- replays under a HIP graph.
+ * aphro_wna16_gemm_large_g32_supported: 1 exactly when the kernel takes the shape -- f16 | bf16, M >= 1, N % 128 == 0,
+ * K % 64 == 0, groups * 32 == K, and a, q_weight, c and scales each below 4 GiB.
+ * aphro_wna16_gemm_large_g32_workspace_bytes: the f16 copy of bf16 activations + the fp32 slabs of the plan for the shape
+ * (0 for an unsupported shape); workspace 16-byte aligned, APHRO_ERR_WORKSPACE without a launch when it is too small. */
+int aphro_wna16_gemm_large_g32_supported(int64_t M, int64_t N, int64_t K, int64_t groups, int dtype);
+size_t aphro_wna16_gemm_large_g32_workspace_bytes(int64_t M, int64_t N, int64_t K, int64_t groups, int dtype);
+int aphro_wna16_gemm_large_g32(const void* a, int64_t lda, const uint32_t* q_weight, const uint32_t* qzeros,
+                               const void* scales, void* c, void* workspace, size_t workspace_bytes, int64_t M, int64_t N,
+                               int64_t K, int64_t groups, int zero_offset, int dtype, void* stream);
+
 /* `_C::gptq_gemm` with use_exllama = false, bit = 4 at decode sizes: the role of gemm_half_q_half_alt_4bit_kernel
  * (q_gemm.cu:1184-1281, launched by gemm_half_q_half_alt :1283-1310 for up to 8 rows), the kernel of act-order checkpoints
  * under row-parallel TP (gptq.py:137-139 keeps those layers in checkpoint order).  csrc/gptq_gidx_gemm.hip.
