@@ -922,6 +922,16 @@ def gptq_gemm(a: torch.Tensor, b_q_weight: torch.Tensor,
 GPTQ8_LARGE_MIN_M = 65
 GPTQ8_LARGE_MAX_M = 1024
 
+# Routed rows per expert (T * topk / E) from which an int4 sparse MLP goes to the prompt-sized grouped kernel
+# (csrc/moe_wna16_gemm_large.hip: 128-row tiles, the gather in the loader) instead of the decode-sized grouped kernel behind
+# moe_gather_pack.  The smallest measured T * topk / E from which the whole layer is faster at BOTH Mixtral-8x7B shapes (E 8,
+# top-2, H 4096, I 14336 and its TP-4 slice 3584; f16, group 128; tools/moe_prefill_bench.py, profiles/moe_wna16_gemm_large.txt,
+# DESIGN.md "moe_wna16_gemm_large").  Old / new time per layer at I = 14336 / 3584:
+#   rows/E =   32: 0.70 / 0.48      64: 1.04 / 0.77 (128-row tiles at most half full)      128: 1.65 / 1.23      256: 1.95 / 1.46
+#   rows/E =  512: 2.40 / 1.76    1024: 2.53 / 2.07    2048 (T = 8192): 2.64 / 2.06
+# It wins everywhere from 128 up, so there is no upper bound; 65 .. 127 rows per expert were not measured.
+MOE_WNA16_LARGE_MIN_ROWS = 128
+
 
 def gptq8_large_ok(m: int, n: int, k: int, groups: int, dtype: torch.dtype) -> bool:
     return dtype in _DT and bool(_lib.lib().aphro_gptq8_gemm_large_supported(m, n, k, groups, _dt_of(dtype)))
@@ -2179,6 +2189,60 @@ def moe_combine(slabs: torch.Tensor, inv_pos: torch.Tensor, topk_weights: torch.
     odt = _lib.F16 if out_dtype == torch.float16 else _lib.BF16
     check(_lib.lib().aphro_moe_combine(out.data_ptr(), slabs.data_ptr(), nslab, m_pad, inv_pos.data_ptr(),
                                        topk_weights.data_ptr(), t_, topk, n, odt, _stream()), "moe_combine")
+    return out
+
+
+MOE_LARGE_BLOCK_M = 128   # the row tile of csrc/moe_wna16_gemm_large.hip = the block size its callers align to
+_MOE_LARGE_MODES = {"out": 0, "silu": 1, "slab": 2}
+
+
+def moe_wna16_large_ok(m_pad: int, n: int, k: int, groups: int, num_experts: int, dtype: torch.dtype) -> bool:
+    return dtype in _DT and bool(_lib.lib().aphro_moe_wna16_gemm_large_supported(m_pad, n, k, groups, num_experts,
+                                                                                 _dt_of(dtype)))
+
+
+def wna16_gemm_grouped_large(a: torch.Tensor, sorted_ids: Optional[torch.Tensor], topk: int, qweight: torch.Tensor,
+                             qzeros: torch.Tensor, scales: torch.Tensor, expert_ids: torch.Tensor,
+                             num_tokens_post_pad: torch.Tensor, zero_offset: int, mode: str, bn: int = 0) -> torch.Tensor:
+    """Grouped expert GEMM at prompt sizes (csrc/moe_wna16_gemm_large.hip) over moe_align_block_size(topk_ids, 128, E):
+    row r of the result is a[sorted_ids[r] // topk] (sorted_ids None: a[r]) times the int4 weights of expert
+    expert_ids[r // 128].  qweight [E, K/8, N] exllama order, qzeros [E, G, N/8], scales [E, G, N].  mode "out" -> [m_pad, N]
+    in scales.dtype; "silu" (interleaved gate/up columns) -> SiluAndMul activations, f16 [m_pad, N/2]; "slab" -> fp32
+    [1, m_pad, N] for moe_combine (which applies the routed weights).  Rows of skipped tiles (past num_tokens_post_pad) are
+    not written.  bn: 0 = planned column tile, 128 / 256 force it."""
+    _require_cuda(a, qweight, qzeros, scales, expert_ids, num_tokens_post_pad)
+    if mode not in _MOE_LARGE_MODES:
+        raise RuntimeError(f"wna16_gemm_grouped_large: unknown mode {mode!r}")
+    e, k8, n = qweight.shape
+    k, groups = k8 * 8, scales.shape[1]
+    m_pad = expert_ids.numel() * MOE_LARGE_BLOCK_M
+    if a.shape[1] != k or tuple(qzeros.shape) != (e, groups, n // 8) or tuple(scales.shape) != (e, groups, n):
+        raise RuntimeError("wna16_gemm_grouped_large: shape mismatch")
+    if expert_ids.dtype != torch.int32 or num_tokens_post_pad.dtype != torch.int32 or \
+            (sorted_ids is not None and (sorted_ids.dtype != torch.int32 or not sorted_ids.is_contiguous())):
+        raise RuntimeError("wna16_gemm_grouped_large: sorted_ids / expert_ids / num_tokens_post_pad must be int32")
+    if not moe_wna16_large_ok(m_pad, n, k, groups, e, scales.dtype):
+        raise RuntimeError(f"wna16_gemm_grouped_large: m_pad={m_pad} N={n} K={k} groups={groups} {scales.dtype} is not served "
+                           "by the kernel")
+    if a.stride(1) != 1 or a.stride(0) % 8 != 0 or a.data_ptr() % 16 != 0:
+        a = a.contiguous()
+    qweight, qzeros, scales, expert_ids = qweight.contiguous(), qzeros.contiguous(), scales.contiguous(), expert_ids.contiguous()
+    dev = a.device
+    if mode == "silu":
+        out = torch.empty((m_pad, n // 2), dtype=torch.float16, device=dev)
+    elif mode == "slab":
+        out = torch.empty((1, m_pad, n), dtype=torch.float32, device=dev)
+    else:
+        out = torch.empty((m_pad, n), dtype=scales.dtype, device=dev)
+    lib = _lib.lib()
+    nbytes = lib.aphro_moe_wna16_gemm_large_workspace_bytes(a.shape[0], k, _dt(a))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None      # (the caching allocator: capturable)
+    check(lib.aphro_moe_wna16_gemm_large(a.data_ptr(), a.shape[0], a.stride(0), _dt(a), _ptr(sorted_ids),
+                                         sorted_ids.numel() if sorted_ids is not None else 0, topk, qweight.data_ptr(),
+                                         qzeros.data_ptr(), scales.data_ptr(), expert_ids.data_ptr(),
+                                         num_tokens_post_pad.data_ptr(), out.data_ptr(), _ptr(ws), nbytes, m_pad, n, k, groups, e,
+                                         zero_offset, _dt(scales), _MOE_LARGE_MODES[mode], bn, _stream()),
+          "wna16_gemm_grouped_large")
     return out
 
 

@@ -71,6 +71,9 @@ SIGNATURES = {
     "aphro_wna16_grouped_ksplit": (I, [L, L, L, L]),
     "aphro_wna16_gemm_grouped": (I, [P, P, P, P, P, P, P, P, Z, P, L, L, L, L, I, I, P]),
     "aphro_moe_combine": (I, [P, P, I, L, P, P, L, I, L, I, P]),
+    "aphro_moe_wna16_gemm_large_supported": (I, [L, L, L, L, L, I]),
+    "aphro_moe_wna16_gemm_large_workspace_bytes": (Z, [L, L, I]),
+    "aphro_moe_wna16_gemm_large": (I, [P, L, L, I, P, L, I, P, P, P, P, P, P, P, Z, L, L, L, L, L, I, I, I, I, P]),
     "aphro_fused_add_rms_norm_pack": (I, [P, P, I, P, I, P, F, P, P, L, I, I, P]),
     "aphro_silu_and_mul_pack_slabs": (I, [P, I, P, P, L, I, I, P]),
     "aphro_silu_and_mul_pack": (I, [P, P, P, L, I, I, P]),

@@ -11,6 +11,10 @@ weights read once):
     wna16_gemm_grouped(w13, silu_pack)  [gate_j, up_j interleaved] -> SiluAndMul in the epilogue
     wna16_gemm_grouped(w2, slabs)       fp32 split-K slabs
     moe_combine                         routed weight, sum over top-k
+
+From ``ops.MOE_WNA16_LARGE_MIN_ROWS`` routed rows per expert (prompts) the two GEMMs are the prompt-sized grouped kernel
+(``csrc/moe_wna16_gemm_large.hip``, ``moe_large_routed``): block 128, the gather inside GEMM 1's loader, GEMM 2 into one fp32
+slab, the same ``moe_combine``.
 """
 import abc
 from typing import Callable, List, Optional, Tuple
@@ -66,8 +70,9 @@ class DeferredCombine:
 
 
 def route_and_align(hidden_states: torch.Tensor, gating_output: torch.Tensor, topk: int, renormalize: bool,
-                    num_experts: int, want_inverse: bool = False, custom_routing_function: Optional[Callable] = None):
-    """fused_topk + moe_align_block_size(MOE_BLOCK_M): ONE launch for decode-sized batches (ops.moe_route_align), the
+                    num_experts: int, want_inverse: bool = False, custom_routing_function: Optional[Callable] = None,
+                    block: int = MOE_BLOCK_M):
+    """fused_topk + moe_align_block_size(block): ONE launch for decode-sized batches (ops.moe_route_align), the
     separate ops above otherwise -- same results either way.  Returns (topk_weights, topk_ids, sorted_ids, expert_ids,
     num_tokens_post_pad, inv or None).  ``custom_routing_function`` (FusedMoE.select_experts, layer.py:400-430): the
     model's own routing, called as the reference calls it, then aligned."""
@@ -77,19 +82,19 @@ def route_and_align(hidden_states: torch.Tensor, gating_output: torch.Tensor, to
         topk_weights, topk_ids = custom_routing_function(hidden_states=hidden_states, gating_output=gating_output,
                                                          topk=topk, renormalize=renormalize)
         topk_weights, topk_ids = topk_weights.float().contiguous(), topk_ids.to(torch.int32).contiguous()
-        out = moe_align_block_size(topk_ids, MOE_BLOCK_M, num_experts, want_inverse=want_inverse)
+        out = moe_align_block_size(topk_ids, block, num_experts, want_inverse=want_inverse)
         return (topk_weights, topk_ids) + tuple(out) + (() if want_inverse else (None, ))
     # the one-workgroup launcher's own limits (csrc/moe.hip aphro_moe_route_align): <= 256 experts, topk <= experts, and
     # (slots + 66 E + 1) int32 of LDS <= 64 KB -- e.g. E = 128 with top-8 stops at 991 tokens, E >= 249 is never served.
     # Outside them the separate ops below handle the call (the launcher's check used to surface as a RuntimeError)
-    if (0 < t_ * topk <= ops.MOE_ROUTE_ALIGN_MAX_SLOTS and topk <= 8 and topk <= num_experts <= 256
+    if (block == MOE_BLOCK_M and 0 < t_ * topk <= ops.MOE_ROUTE_ALIGN_MAX_SLOTS and topk <= 8 and topk <= num_experts <= 256
             and (t_ * topk + 66 * num_experts + 1) * 4 <= 64 * 1024
             and gating_output.stride(1) == 1
             and gating_output.dtype in (torch.float16, torch.bfloat16, torch.float32)
             and not switch("APHRO_MOE_NO_ROUTE_ALIGN")):
         return ops.moe_route_align(gating_output, topk, renormalize, num_experts, MOE_BLOCK_M, want_inverse)
     topk_weights, topk_ids = fused_topk(hidden_states, gating_output, topk, renormalize)
-    out = moe_align_block_size(topk_ids, MOE_BLOCK_M, num_experts, want_inverse=want_inverse)
+    out = moe_align_block_size(topk_ids, block, num_experts, want_inverse=want_inverse)
     return (topk_weights, topk_ids) + tuple(out) + (() if want_inverse else (None, ))
 
 
@@ -127,16 +132,56 @@ class Wna16Experts:
         self.inter = self.w2[0].shape[1] * 8
 
 
+def moe_large_routed(num_tokens: int, topk: int, experts: Wna16Experts, dtype: torch.dtype) -> bool:
+    """The one routing rule of the prompt-sized grouped kernel (csrc/moe_wna16_gemm_large.hip): at least
+    ops.MOE_WNA16_LARGE_MIN_ROWS routed rows per expert, and both expert GEMMs served at the 128-aligned row count."""
+    e = experts.num_experts
+    if num_tokens * topk < ops.MOE_WNA16_LARGE_MIN_ROWS * e or experts.w13[2].dtype != dtype:
+        return False
+    bm = ops.MOE_LARGE_BLOCK_M
+    m_pad = (num_tokens * topk + e * (bm - 1) + bm - 1) // bm * bm
+    return (ops.moe_wna16_large_ok(m_pad, experts.w13[0].shape[2], experts.hidden, experts.w13[2].shape[1], e, dtype)
+            and ops.moe_wna16_large_ok(m_pad, experts.hidden, experts.inter, experts.w2[2].shape[1], e, dtype))
+
+
+def _fused_wna16_moe_large(hidden_states, experts, gating_output, topk, renormalize, topk_weights, topk_ids, defer_combine):
+    """Prompt-sized form (3 launches after routing): align at block 128, GEMM 1 with the gather in its loader and SiluAndMul
+    in its epilogue, GEMM 2 into one fp32 slab, moe_combine."""
+    e = experts.num_experts
+    if topk_ids is None:
+        topk_weights, topk_ids, sorted_ids, expert_ids, post_pad, inv = route_and_align(
+            hidden_states, gating_output, topk, renormalize, e, want_inverse=True, block=ops.MOE_LARGE_BLOCK_M)
+    else:       # (a caller's block-16 alignment does not serve 128-row tiles: aligned again)
+        sorted_ids, expert_ids, post_pad, inv = moe_align_block_size(topk_ids, ops.MOE_LARGE_BLOCK_M, e, want_inverse=True)
+    qw, qz, sc = experts.w13
+    act = ops.wna16_gemm_grouped_large(hidden_states, sorted_ids, topk, qw, qz, sc, expert_ids, post_pad,
+                                       experts.zero_offset, "silu")
+    qw, qz, sc = experts.w2
+    slabs = ops.wna16_gemm_grouped_large(act, None, 1, qw, qz, sc, expert_ids, post_pad, experts.zero_offset, "slab")
+    if defer_combine:
+        return DeferredCombine(slabs, inv, topk_weights.contiguous(), hidden_states.dtype)
+    return ops.moe_combine(slabs, inv, topk_weights.contiguous(), hidden_states.dtype)
+
+
 def fused_wna16_moe(hidden_states: torch.Tensor, experts: Wna16Experts, gating_output: torch.Tensor,
                     topk: int, renormalize: bool = True,
                     topk_weights: Optional[torch.Tensor] = None,
-                    topk_ids: Optional[torch.Tensor] = None, aligned=None, defer_combine: bool = False):
+                    topk_ids: Optional[torch.Tensor] = None, aligned=None, defer_combine: bool = False,
+                    large: Optional[bool] = None):
     """The fused_marlin_moe role (fused_moe.py:438-542) for GPTQ/AWQ int4 experts.  aligned: (sorted_ids, expert_ids,
-    post_pad, inv) when the caller has routed and aligned already (route_and_align)."""
+    post_pad, inv) when the caller has routed and aligned already (route_and_align).  large: None = the prompt-sized grouped
+    kernel where moe_large_routed says so; False = never (the decode-sized path below); True = wherever it serves the shapes."""
     assert hidden_states.shape[1] == experts.hidden, "Hidden size mismatch"
     assert gating_output.shape[1] == experts.num_experts, "Number of experts mismatch"
     m = hidden_states.shape[0]
     e = experts.num_experts
+    if large is None:
+        large = moe_large_routed(m, topk, experts, hidden_states.dtype)
+    elif large and (m == 0 or experts.w13[2].dtype != hidden_states.dtype):
+        raise RuntimeError("fused_wna16_moe: the prompt-sized grouped kernel needs rows, and scales of the activations' dtype")
+    if large:       # (a shape the kernel refuses is an error of wna16_gemm_grouped_large when forced)
+        return _fused_wna16_moe_large(hidden_states, experts, gating_output, topk, renormalize, topk_weights, topk_ids,
+                                      defer_combine)
     packed = None
     if aligned is not None:
         sorted_ids, expert_ids, post_pad, inv = aligned

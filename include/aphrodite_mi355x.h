@@ -873,6 +873,31 @@ int aphro_moe_combine(void* out, const float* slabs, int nslab, int64_t m_pad,
                       const int32_t* inv_pos, const float* topk_weights, int64_t num_tokens,
                       int topk, int64_t N, int dtype, void* stream);
 
+/* Grouped expert GEMM for PROMPT-sized batches (the marlin_gemm_moe role at ~hundreds of rows per expert), over the rows
+ * of moe_align_block_size at BLOCK SIZE 128.  csrc/moe_wna16_gemm_large.hip.
+ *   out[r, :] = a[row(r), :] . W_e,  e = expert_ids[r / 128],  W_e[k][n] = (q_e[k][n] - (z_e[k / gs][n] + zero_offset)) * s_e[k / gs][n]
+ * a: [a_rows, lda] f16 | bf16 (a_dtype; lda in elements, lda % 8 == 0, lda >= K, 16-byte aligned).  sorted_token_ids
+ * [sorted_len]: row(r) = sorted_token_ids[r] / topk, clamped to a_rows - 1 (padding ids); null: row(r) = r, a_rows >= m_pad.
+ * q_weight int32 [E, K/8, N] exllama order; qzeros int32 [E, groups, N/8]; scales [E, groups, N] in `dtype`.
+ * expert_ids int32 [m_pad / 128], num_tokens_post_pad int32 [1]: 128-row tiles past the padded count or with an expert id
+ * outside 0 .. num_experts - 1 are skipped on the device (their rows of `out` are not written); nothing synchronises with
+ * the host.  mode 0: out [m_pad, N] in `dtype`.  mode 1 (N = interleaved (gate_j, up_j) columns): out = F16 [m_pad, N / 2],
+ * round(round(silu(round(gate))) * round(up)) in `dtype` (the arithmetic of aphro_wna16_gemm_large_silu), a bf16 result
+ * stored as f16.  mode 2: out = fp32 [m_pad, N], one slab for aphro_moe_combine.  bn: 0 (planned from the tile count) or
+ * 128 / 256, the column tile.  Arithmetic of aphro_wna16_gemm_large; bf16 activations are widened to f16 with saturation
+ * into the workspace (aphro_moe_wna16_gemm_large_workspace_bytes: 0 for f16), 16-byte aligned, APHRO_ERR_WORKSPACE without
+ * a launch when it is too small.
+ * aphro_moe_wna16_gemm_large_supported: 1 exactly when the kernel takes the shape -- f16 | bf16, m_pad % 128 == 0,
+ * N % 128 == 0, K % 128 == 0, group size K / groups = 128 x 2^n, one expert's tensors and the outputs each below 4 GiB. */
+int aphro_moe_wna16_gemm_large_supported(int64_t m_pad, int64_t N, int64_t K, int64_t groups, int64_t num_experts, int dtype);
+size_t aphro_moe_wna16_gemm_large_workspace_bytes(int64_t a_rows, int64_t K, int a_dtype);
+int aphro_moe_wna16_gemm_large(const void* a, int64_t a_rows, int64_t lda, int a_dtype, const int32_t* sorted_token_ids,
+                               int64_t sorted_len, int topk, const uint32_t* q_weight, const uint32_t* qzeros,
+                               const void* scales, const int32_t* expert_ids, const int32_t* num_tokens_post_pad,
+                               void* out, void* workspace, size_t workspace_bytes, int64_t m_pad, int64_t N, int64_t K,
+                               int64_t groups, int64_t num_experts, int zero_offset, int dtype, int mode, int bn,
+                               void* stream);
+
 /* ------------------------------------------------------------------------
  * Per-step bookkeeping inside the HIP graph
  * ---------------------------------------------------------------------- */
